@@ -111,6 +111,33 @@ def make_u(torch, dev, model, pots, amp, n, T, fs=FS):
     return u
 
 
+DUMP_BYTES = 60_000_000    # --dump-outputs: all files together stay below 64 MB
+
+
+def dump_sample(shape, budget, seed=20251015):
+    """(instances, samples): the fixed, seeded part of an output y [n, T, ny] (float64) that --dump-outputs writes within
+    `budget` bytes -- every instance if they all fit, else a seeded choice of instances; if one instance's samples alone
+    exceed the budget, a seeded choice of its samples as well.  Both index lists are sorted."""
+    n, T, ny = shape
+    rng = np.random.Generator(np.random.PCG64(seed))
+    row = 8 * T * max(ny, 1)
+    k = min(n, max(1, budget // row))
+    inst = np.arange(n) if k == n else np.sort(rng.choice(n, k, replace=False))
+    t = np.arange(T) if row <= budget else np.sort(rng.choice(T, max(1, budget // (8 * max(ny, 1))), replace=False))
+    return inst, t
+
+
+def dump_outputs(out_dir, name, y, budget):
+    """Writes the sample of y [n, T, ny] that dump_sample picks as out_dir/<name>.npy (float64); returns its description."""
+    import torch
+    inst, t = dump_sample(tuple(y.shape), budget)
+    sel = y.index_select(0, torch.as_tensor(inst, device=y.device)).index_select(1, torch.as_tensor(t, device=y.device))
+    arr = np.ascontiguousarray(sel.cpu().numpy(), dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, name + ".npy"), arr)
+    return {"file": name + ".npy", "shape": list(arr.shape), "of": list(y.shape), "instances": len(inst), "samples": len(t)}
+
+
 def pmc_record(workload, n, T, solver=None, kernel=None, kernel_ms=None):
     """The committed rocprofv3 PMC passes of THIS run's configuration (profiles/pmc_traffic.json, written by
     tools/profile_gpu.sh: separate --pmc runs of the same command), or None.  A record only counts if it was taken
@@ -710,7 +737,13 @@ def main():
                          "several minutes; all 16 384 instances of config 5 on one GPU among them)")
     ap.add_argument("--no-literal-grid", action="store_true",
                     help="skip the leg on the LITERAL config-3 grid, drive = linspace(0, 1, 32) with its singular column (config.literal_grid)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output y [instances, samples, ny] of the last timed step as DIR/y.npy "
+                         "(DIR/y_rank<r>.npy per rank when N > 1), float64: all of it, or a fixed seeded sample of instances "
+                         "(bench.dump_sample) that keeps the files below 64 MB together")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     import torch
     import torch.distributed as dist
@@ -818,6 +851,9 @@ def main():
         iters_total, n_warn, n_dead, iters_max = (float(stats[1]), float(stats[2]), float(stats[3]),
                                                   float(stats[4]))
     checksum = float(torch.nan_to_num(y).abs().sum())
+    dumped = None
+    if args.dump_outputs:      # y still holds the last timed step's output: nothing has run on it since
+        dumped = dump_outputs(args.dump_outputs, "y" if world == 1 else f"y_rank{rank}", y, DUMP_BYTES // world)
     checksums = [checksum]
     if use_dist:       # every rank's output checksum (shards must differ: other grid cells / other seeds)
         cs = [None] * world
@@ -939,6 +975,7 @@ def main():
                 "n_warn": n_warn, "n_nonfinite_instances": n_dead, "y_abs_sum_rank0": checksum,
                 "y_abs_sum_per_rank": checksums,
                 **({"host_setup": setup} if setup else {}),
+                **({"dump_outputs": dumped} if dumped else {}),
             },
             "roofline": {
                 "bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",

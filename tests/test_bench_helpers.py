@@ -119,3 +119,23 @@ def test_native_cpu_leg_times_the_native_build():
     finally:
         os.environ.pop("ACME_REF_LIB", None)
         os.remove(native)
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path):
+    """--dump-outputs: the whole output when it fits, else the same seeded instances (and, for one over-long instance, the
+    same seeded samples) on every run, within the byte budget; the file holds exactly those entries of y, in float64."""
+    import torch
+    for shape in ((8192, 44100, 1), (8192, 4410, 1), (2048, 176400, 1), (3, 40, 4), (2, 10_000_000, 1)):
+        inst, t = bench.dump_sample(shape, bench.DUMP_BYTES)
+        again = bench.dump_sample(shape, bench.DUMP_BYTES)
+        assert np.array_equal(inst, again[0]) and np.array_equal(t, again[1])
+        assert 8 * len(inst) * len(t) * shape[2] <= bench.DUMP_BYTES
+        assert (np.diff(inst) > 0).all() and (np.diff(t) > 0).all() and inst[-1] < shape[0] and t[-1] < shape[1]
+        if 8 * shape[0] * shape[1] * shape[2] <= bench.DUMP_BYTES:
+            assert len(inst) == shape[0] and len(t) == shape[1]
+    y = torch.randn((300, 50_000, 1), dtype=torch.float64, generator=torch.Generator().manual_seed(1))
+    rec = bench.dump_outputs(str(tmp_path / "out"), "y", y, 20_000_000)
+    arr = np.load(tmp_path / "out" / "y.npy")
+    inst, t = bench.dump_sample(tuple(y.shape), 20_000_000)
+    assert arr.dtype == np.float64 and arr.nbytes <= 20_000_000 and rec["shape"] == list(arr.shape) == [len(inst), 50_000, 1]
+    assert np.array_equal(arr, y.numpy()[inst][:, t])
