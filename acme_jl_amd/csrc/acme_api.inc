@@ -1,6 +1,7 @@
 // acme_api.inc -- C ABI implementation (include/acme_hip.h), written against a tiny device
 // backend `be::` so that the HIP library (acme_hip.hip) and the CPU wave emulator used by the
 // GPU-less unit tests (tests/emu) share every line of host logic.  Included, not compiled alone.
+#include "acme_resample.h"
 // ------------------------------------------------------------------------------------------
 // handles
 // ------------------------------------------------------------------------------------------
@@ -121,6 +122,18 @@ struct acme_batch {
     int *d_coop_order = nullptr;       // [N][64]: the row order each instance has learnt (kept between launches)
     GenHeader *d_gh = nullptr;
     double *d_ws = nullptr;
+    // Oversampled runs (acme_batch_set_oversampling, acme_resample.h): the model advances k samples per sample of u / y
+    struct Oversampling {
+        int k = 1;                               // 1: off (none of the members below is used)
+        int lu = 0, ld = 0, du = 0;              // tap counts; du = (lu - 1) / k base-rate samples of u history
+        unsigned long long held = 0;             // input rows held (zero-order hold)
+        bool fresh = true;                       // the next run extends each signal's first sample into the past
+        double *d_taps = nullptr;                // k h_up | h_down
+        double *d_hist_u = nullptr, *d_hist_y = nullptr;    // [N][du][nu], [N][ld - 1][ny]
+        double *d_ou = nullptr, *d_oy = nullptr, *d_base = nullptr;   // a slice at the model rate (u, y); full u rows
+        size_t cap_ou = 0, cap_oy = 0, cap_base = 0;
+        be::event_t ev[2] = {};                  // host-buffer runs: slice s has been decimated
+    } os;
     // acme_batch_run_async: the run in flight on a worker thread of the library, its status and message
     std::thread worker;
     int worker_rc = ACME_OK;
@@ -688,6 +701,9 @@ void acme_batch_destroy(acme_batch *b) {
     (void)be::dfree(b->d_map_fast); (void)be::dfree(b->d_map_slow);
     (void)be::dfree(b->d_map_bal); (void)be::dfree(b->d_bal_prev); (void)be::dfree(b->d_bal_weight);
     (void)be::flag_free(b->h_u_ready);
+    (void)be::dfree(b->os.d_taps); (void)be::dfree(b->os.d_hist_u); (void)be::dfree(b->os.d_hist_y);
+    (void)be::dfree(b->os.d_ou); (void)be::dfree(b->os.d_oy); (void)be::dfree(b->os.d_base);
+    for (auto &e : b->os.ev) if (e) (void)be::event_destroy(e);
     for (int i = 0; i < acme_batch::NEV; ++i) {
         if (b->ev0[i]) (void)be::event_destroy(b->ev0[i]);
         if (b->ev1[i]) (void)be::event_destroy(b->ev1[i]);
@@ -808,7 +824,20 @@ static int rebuild_on_plain_shape(acme_batch *b) {
     nb->retain_host = b->retain_host;
     nb->iso_thr = b->iso_thr;
     nb->balance = b->balance;
+    std::swap(nb->os, b->os);    // (oversampling: factor, taps, the signals' past and scratch go with the instances)
     std::swap(*b, *nb);          // (b is the plain-shape batch now; the guard destroys what it was)
+    return ACME_OK;
+}
+
+// the instances acme_batch_set_matrices makes afresh start an oversampled batch's histories from zero (a batch that has not
+// run since acme_batch_set_oversampling extends the first samples into the past at its next run instead)
+static int os_zero_history(acme_batch *b, long long first, long long count) {
+    const acme_batch::Oversampling &O = b->os;
+    if (O.k == 1 || O.fresh) return ACME_OK;
+    const size_t hu = (size_t)O.du * b->P.actual.nu, hy = (size_t)(O.ld - 1) * b->P.actual.ny;
+    std::vector<double> z((size_t)count * (hu > hy ? hu : hy), 0.0);
+    if (hu) HIPCHK(be::copy_h2d(O.d_hist_u + (size_t)first * hu, z.data(), sizeof(double) * (size_t)count * hu));
+    if (hy) HIPCHK(be::copy_h2d(O.d_hist_y + (size_t)first * hy, z.data(), sizeof(double) * (size_t)count * hy));
     return ACME_OK;
 }
 
@@ -861,7 +890,7 @@ int acme_batch_set_matrices(acme_batch *b, long long first, long long count, con
             const std::vector<int> ord = coop_initial_order(b->G.H, (size_t)count);
             HIPCHK(be::copy_h2d(b->d_coop_order + (size_t)first * COOP_MAX_N, ord.data(), sizeof(int) * ord.size()));
         }
-        return ACME_OK;
+        return os_zero_history(b, first, count);
     }
     for (int attempt = 0;; ++attempt) {          // (a second pass after a rebuild on the plain shape)
         const size_t img = b->P.image.size();
@@ -919,7 +948,7 @@ int acme_batch_set_matrices(acme_batch *b, long long first, long long count, con
             if (b->inst_models.size() != (size_t)b->N) b->inst_models.resize((size_t)b->N);
             for (long long i = 0; i < count; ++i) b->inst_models[(size_t)(first + i)] = std::make_unique<HostModel>(models[i]->h);
         }
-        return ACME_OK;
+        return os_zero_history(b, first, count);
     }
 }
 
@@ -1171,6 +1200,126 @@ static bool streamed_fits(const acme_batch *b) {
     return blocks <= per_cu * cus;
 }
 
+// ---- oversampled runs (acme_batch_set_oversampling) -----------------------------------------------------------------------
+// Time slice by time slice on the launch stream: [put the full input rows together (run_const)] -> interpolate to the model
+// rate (acme_resample.h) -> the UNCHANGED run kernel over k x the slice's samples -> decimate; the histories carry the
+// signals' past from slice to slice and call to call.  The model-rate scratch is one slice's (ACME_OS_SLICE base-rate
+// samples, default 4 096: config 5 -- 2 048 instances at k = 4 -- 0.8 GB).  Host buffers: the staged pipeline of run_impl, two
+// staging buffers each way, the copies of slices s + 1 (in) and s - 1 (out) beside slice s; never the streamed path.
+static long long os_slice(long long T) {
+    long long TS = 4096;
+    if (const char *e = getenv("ACME_OS_SLICE")) { const long long v = atoll(e); if (v >= 1) TS = v; }
+    return T < TS ? T : TS;
+}
+static int os_grow(double **p, size_t *cap, size_t bytes) {
+    if (bytes > *cap) {
+        (void)be::dfree(*p); *p = nullptr; *cap = 0;
+        HIPCHK(be::dmalloc((void **)p, bytes));
+        *cap = bytes;
+    }
+    return ACME_OK;
+}
+// u: [N][T][nu], or -- const_mask != 0 -- the varying rows [N][T][nuv] and u_const [N][nu] (acme_batch_run_const)
+static int run_os(acme_batch *b, const double *u, const double *u_const, unsigned long long const_mask, double *y, long long T,
+                  int mem, be::stream_t st) {
+    acme_batch::Oversampling &O = b->os;
+    const int k = O.k, nu = b->P.actual.nu, ny = b->P.actual.ny;
+    const size_t N = (size_t)b->N;
+    int nin = nu;                               // rows of u as the caller hands them over
+    for (int r = 0; r < nu && r < 64; ++r) nin -= (const_mask >> r & 1ull) ? 1 : 0;
+    const bool host = mem == ACME_MEM_HOST, expand = const_mask != 0ull;
+    const long long TS = os_slice(T), ns = (T + TS - 1) / TS;
+    auto len = [&](long long s) { return (s + 1) * TS <= T ? TS : T - s * TS; };
+    int rc = os_grow(&O.d_ou, &O.cap_ou, sizeof(double) * N * (size_t)(k * TS) * nu);
+    if (rc == ACME_OK) rc = os_grow(&O.d_oy, &O.cap_oy, sizeof(double) * N * (size_t)(k * TS) * ny);
+    if (rc == ACME_OK && expand) rc = os_grow(&O.d_base, &O.cap_base, sizeof(double) * N * (size_t)TS * nu);
+    if (rc == ACME_OK && host) rc = ensure_staging(b, 2 * sizeof(double) * N * (size_t)TS * nin, 2 * sizeof(double) * N * (size_t)TS * ny);
+    if (rc == ACME_OK && host && expand) rc = os_grow(&b->d_uc, &b->cap_uc, sizeof(double) * N * (size_t)nu);
+    if (rc != ACME_OK) return rc;
+    const double *uc = u_const;
+    if (host && expand) {
+        HIPCHK(be::copy_h2d_async(b->d_uc, u_const, sizeof(double) * N * (size_t)nu, st));
+        uc = b->d_uc;
+    }
+    auto ubuf = [&](long long s) { return b->d_u + (s & 1) * (N * (size_t)TS * nin); };
+    auto ybuf = [&](long long s) { return b->d_y + (s & 1) * (N * (size_t)TS * ny); };
+    const double *g = O.d_taps, *h = O.d_taps + O.lu;
+    // slice s on the launch stream
+    auto slice = [&](long long s) -> int {
+        const long long n = len(s), nk = n * k;
+        const double *src = host ? ubuf(s) : u + (size_t)s * TS * nin;
+        long long pitch = host ? n : T;
+        if (expand) {
+            HIPCHK(be::launch_expand(O.d_base, src, uc, const_mask, (long long)N, n, pitch, nu, nin, st));
+            src = O.d_base;
+            pitch = n;
+        }
+        if (nu) {
+            OsHistArgs H{O.d_hist_u, src, (long long)N, n, pitch, nu, O.du};
+            if (O.fresh) HIPCHK(os_launch_hist(H, true, st));
+            const OsInterpArgs I{src, O.d_hist_u, O.d_ou, g, (long long)N, n, pitch, nu, O.lu, O.du, O.held | const_mask};
+            HIPCHK(os_launch_interp(k, I, st));
+            HIPCHK(os_launch_hist(H, false, st));
+        }
+        const int rc_ = launch_run(b, O.d_ou, O.d_oy, nk, st, nullptr);
+        if (rc_ != ACME_OK) return rc_;
+        if (ny) {
+            OsHistArgs H{O.d_hist_y, O.d_oy, (long long)N, nk, nk, ny, O.ld - 1};
+            if (O.fresh) HIPCHK(os_launch_hist(H, true, st));
+            double *dst = host ? ybuf(s) : y + (size_t)s * TS * ny;
+            const OsDecimArgs D{O.d_oy, O.d_hist_y, dst, h, (long long)N, n, host ? n : T, k, ny, O.ld};
+            HIPCHK(os_launch_decim(D, st));
+            HIPCHK(os_launch_hist(H, false, st));
+        }
+        O.fresh = false;
+        return ACME_OK;
+    };
+    if (!host) {
+        for (long long s = 0; s < ns; ++s) {
+            rc = slice(s);
+            if (rc != ACME_OK) return rc;
+        }
+        if (b->progress) b->progress(b->progress_user, T, T);
+        return ACME_OK;
+    }
+    if (!b->retain_host) { release_reg(b->reg_u); release_reg(b->reg_y); }
+    else {
+        (void)ensure_registered(b->reg_u, u, sizeof(double) * N * (size_t)T * (nin ? nin : 1));
+        (void)ensure_registered(b->reg_y, y, sizeof(double) * N * (size_t)T * ny);
+    }
+    if (!b->copy_stream) HIPCHK(be::stream_create_nonblocking(&b->copy_stream));
+    if (!b->copy_stream_out) HIPCHK(be::stream_create_nonblocking(&b->copy_stream_out));
+    const be::stream_t cs = b->copy_stream, cso = b->copy_stream_out;
+    auto copy_in = [&](long long s) -> int {          // (packed: an instance's rows len(s) apart)
+        if (!nin) return 0;
+        const size_t w = sizeof(double) * (size_t)len(s) * nin;
+        return be::copy2d_h2d_async(ubuf(s), w, u + (size_t)s * TS * nin, sizeof(double) * (size_t)T * nin, w, N, cs);
+    };
+    auto copy_out = [&](long long s) -> int {
+        if (!ny) return 0;
+        const size_t w = sizeof(double) * (size_t)len(s) * ny;
+        return be::copy2d_d2h_async(y + (size_t)s * TS * ny, sizeof(double) * (size_t)T * ny, ybuf(s), w, w, N, cso);
+    };
+    HIPCHK(copy_in(0));
+    HIPCHK(be::stream_sync(cs));
+    for (long long s = 0; s < ns; ++s) {
+        rc = slice(s);
+        if (rc != ACME_OK) return rc;
+        HIPCHK(be::event_record(O.ev[s & 1], st));
+        if (s > 0) HIPCHK(be::event_sync(O.ev[(s - 1) & 1]));       // slice s-1 decimated: its buffers are free
+        if (s + 1 < ns) HIPCHK(copy_in(s + 1));                      // both overlap slice s, and each other
+        if (s > 0) HIPCHK(copy_out(s - 1));
+        if (s + 1 < ns) HIPCHK(be::stream_sync(cs));
+        if (s > 0) HIPCHK(be::stream_sync(cso));
+        if (s > 0 && b->progress) b->progress(b->progress_user, s * TS, T);     // (base-rate samples)
+    }
+    HIPCHK(be::event_sync(O.ev[(ns - 1) & 1]));
+    HIPCHK(copy_out(ns - 1));
+    HIPCHK(be::stream_sync(cso));
+    if (b->progress) b->progress(b->progress_user, T, T);
+    return ACME_OK;
+}
+
 static int run_impl(acme_batch *b, const double *u, double *y, long long T, int mem, void *stream);
 int acme_batch_run(acme_batch *b, const double *u, double *y, long long T, int mem, void *stream) {
     join_worker(b);
@@ -1185,6 +1334,10 @@ static int run_impl(acme_batch *b, const double *u, double *y, long long T, int 
     if (T == 0) return ACME_OK;
     ON_DEVICE(b);
     be::stream_t st = (be::stream_t)stream;
+    if (b->os.k > 1) {
+        if (mem != ACME_MEM_HOST && mem != ACME_MEM_DEVICE) return fail(ACME_ERR_INVALID, "mem must be ACME_MEM_HOST or ACME_MEM_DEVICE");
+        return run_os(b, u, nullptr, 0ull, y, T, mem, st);
+    }
     if (mem == ACME_MEM_DEVICE) {
         const int rc_ = launch_run(b, u, y, T, st, nullptr);
         if (rc_ == ACME_OK && b->progress) b->progress(b->progress_user, T, T);
@@ -1416,6 +1569,7 @@ int acme_batch_run_const(acme_batch *b, const double *u_var, const double *u_con
     if (T == 0) return ACME_OK;
     ON_DEVICE(b);
     be::stream_t st = (be::stream_t)stream;
+    if (b->os.k > 1) return run_os(b, u_var, u_const, const_mask, y, T, mem, st);
     const size_t N = (size_t)b->N;
     auto grow = [&](double **p, size_t *cap, size_t bytes) -> int {
         if (bytes > *cap) {
@@ -1546,10 +1700,62 @@ int acme_batch_run_async(acme_batch *b, const double *u, double *y, long long T,
 int acme_batch_set_isolation(acme_batch *b, double iters_per_sample) {
     join_worker(b);
     if (!b || !(iters_per_sample >= 0.0)) return fail(ACME_ERR_INVALID, "invalid argument to acme_batch_set_isolation");
+    if (iters_per_sample > 0.0 && b->os.k > 1)
+        return fail(ACME_ERR_UNSUPPORTED, "isolation of slow instances is not available on an oversampled batch");
     ON_DEVICE(b);
     HIPCHK(be::device_sync());
     b->iso_thr = iters_per_sample;
     if (iters_per_sample == 0.0) { b->map_fast.clear(); b->map_slow.clear(); }
+    return ACME_OK;
+}
+
+int acme_oversampling_design(int factor, double *taps, int capacity) {
+    if (factor < 1 || factor > OS_MAX_FACTOR) return fail(ACME_ERR_INVALID, "oversampling factor must be 1 ... 16");
+    const std::vector<double> h = os_design(factor);
+    if (taps && capacity >= (int)h.size()) memcpy(taps, h.data(), sizeof(double) * h.size());
+    return (int)h.size();
+}
+
+int acme_batch_set_oversampling(acme_batch *b, int factor, const double *h_up, int n_up, const double *h_down, int n_down,
+                                unsigned long long held_rows) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    if (factor < 1 || factor > OS_MAX_FACTOR) return fail(ACME_ERR_INVALID, "oversampling factor must be 1 ... 16");
+    const int nu = b->P.actual.nu, ny = b->P.actual.ny;
+    if ((h_up && (n_up < 1 || n_up > OS_MAX_TAPS)) || (h_down && (n_down < 1 || n_down > OS_MAX_TAPS)))
+        return fail(ACME_ERR_INVALID, "a filter needs 1 ... 4096 taps");
+    if (nu < 64 && (held_rows >> nu) != 0ull) return fail(ACME_ERR_INVALID, "held row beyond the model's inputs");
+    std::vector<double> up = h_up ? std::vector<double>(h_up, h_up + n_up) : os_design(factor);
+    const std::vector<double> down = h_down ? std::vector<double>(h_down, h_down + n_down) : os_design(factor);
+    for (double v : up) if (!std::isfinite(v)) return fail(ACME_ERR_INVALID, "non-finite interpolation tap");
+    for (double v : down) if (!std::isfinite(v)) return fail(ACME_ERR_INVALID, "non-finite decimation tap");
+    if (factor > 1 && b->iso_thr > 0.0)
+        return fail(ACME_ERR_UNSUPPORTED, "oversampling is not available while the isolation of slow instances is in force");
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());          // (a launch still in flight may read the histories)
+    acme_batch::Oversampling &O = b->os;
+    (void)be::dfree(O.d_taps); (void)be::dfree(O.d_hist_u); (void)be::dfree(O.d_hist_y);
+    O.d_taps = O.d_hist_u = O.d_hist_y = nullptr;
+    O.k = 1;
+    O.fresh = true;
+    if (factor == 1) {                  // today's path: nothing of the above is used, the scratch goes
+        (void)be::dfree(O.d_ou); (void)be::dfree(O.d_oy); (void)be::dfree(O.d_base);
+        O.d_ou = O.d_oy = O.d_base = nullptr;
+        O.cap_ou = O.cap_oy = O.cap_base = 0;
+        return ACME_OK;
+    }
+    for (double &v : up) v *= factor;   // g = k h_up: the interpolator's passband gain 1
+    O.lu = (int)up.size();
+    O.ld = (int)down.size();
+    O.du = (O.lu - 1) / factor;
+    O.held = held_rows;
+    up.insert(up.end(), down.begin(), down.end());
+    HIPCHK(be::dmalloc((void **)&O.d_taps, sizeof(double) * up.size()));
+    HIPCHK(be::copy_h2d(O.d_taps, up.data(), sizeof(double) * up.size()));
+    HIPCHK(be::dmalloc((void **)&O.d_hist_u, sizeof(double) * (size_t)b->N * (size_t)O.du * nu));
+    HIPCHK(be::dmalloc((void **)&O.d_hist_y, sizeof(double) * (size_t)b->N * (size_t)(O.ld - 1) * ny));
+    for (auto &e : O.ev) if (!e) HIPCHK(be::event_create(&e));
+    O.k = factor;
     return ACME_OK;
 }
 

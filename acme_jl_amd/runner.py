@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "acme_batch_set_balance", "acme_batch_get_placement",
     "acme_batch_solve", "acme_batch_get_extrapolation_jacobian", "acme_batch_last_kernel_ms", "acme_batch_kernel_time", "acme_batch_get_report", "acme_batch_reset_report",
     "acme_batch_set_resabstol", "acme_batch_get_state", "acme_batch_set_state",
+    "acme_oversampling_design", "acme_batch_set_oversampling",
 ]
 
 
@@ -135,6 +136,8 @@ class Library:
         L.acme_batch_set_resabstol.argtypes = [vp, C.c_double]
         L.acme_batch_get_state.argtypes = [vp, dp, dp, dp]
         L.acme_batch_set_state.argtypes = [vp, dp, dp, dp]
+        L.acme_oversampling_design.argtypes = [C.c_int, dp, C.c_int]
+        L.acme_batch_set_oversampling.argtypes = [vp, C.c_int, dp, C.c_int, dp, C.c_int, C.c_ulonglong]
 
     def check(self, rc):
         if rc < 0:
@@ -157,6 +160,17 @@ def default_library():
 
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def design_oversampling_filter(factor, lib=None):
+    """The library's default lowpass for oversampling by ``factor`` (``acme_oversampling_design``): a linear-phase
+    Kaiser-windowed sinc at the high rate, unit DC gain, passband to 0.40 fs, at least 80 dB from 0.50 fs, length
+    L = 1 (mod factor) and odd.  The one design ``set_oversampling`` uses when no taps are given."""
+    lib = lib or default_library()
+    n = lib.check(lib.L.acme_oversampling_design(int(factor), None, 0))
+    taps = np.zeros(n)
+    lib.check(lib.L.acme_oversampling_design(int(factor), _dp(taps), n))
+    return taps
 
 
 def _ip(a):
@@ -250,6 +264,7 @@ class ModelRunner:
         self.lib.check(self.lib.L.acme_batch_create(self._mh.h, self.n, C.byref(o), C.byref(h)))
         self.h = h
         self._warned = 0
+        self._os = (1, 1, 1)            # oversampling: factor, interpolation taps, decimation taps
         self._progress_cb = None
         if showprogress:
             fn = showprogress if callable(showprogress) else _print_progress
@@ -263,6 +278,48 @@ class ModelRunner:
         run in a launch of their own (``acme_batch_set_isolation``): device-pointer runs then complete on the caller's
         stream for the others, ``wait()`` completes the slow ones.  0 switches it off."""
         self.lib.check(self.lib.L.acme_batch_set_isolation(self.h, float(iters_per_sample)))
+
+    def set_oversampling(self, factor, up=None, down=None, held_rows=()):
+        """Oversampled runs (``acme_batch_set_oversampling``): the model -- derived at ``factor`` x the signal rate -- runs
+        ``factor`` samples per sample of u / y, which every ``run*`` method takes and returns at the BASE rate.  Input rows
+        are interpolated with ``factor * up`` (zero-stuffed), ``held_rows`` held (zero-order hold; the constant rows of
+        ``run_const`` always are), the outputs decimated with ``down``; ``None`` = the library's default lowpass
+        (``design_oversampling_filter``).  The histories of the filters are reset: each signal's first sample extends into
+        the past at the next run, later runs continue where the last ended.  Reports count model-rate samples.
+        ``factor=1`` switches it off."""
+        def taps(h):
+            if h is None:
+                return None, None, 0
+            a = np.ascontiguousarray(np.asarray(h, dtype=np.float64).ravel())
+            return a, _dp(a), len(a)
+        mask = 0
+        for r in held_rows:
+            r = int(r)
+            if r < 0 or r >= 64:          # (the mask has 64 bits; the library refuses rows beyond the model's inputs)
+                raise DimensionMismatch(f"held row {r}: rows 0 ... 63 can be held")
+            mask |= 1 << r
+        ua, up_p, nu_ = taps(up)
+        da, dn_p, nd_ = taps(down)
+        self.lib.check(self.lib.L.acme_batch_set_oversampling(self.h, int(factor), up_p, nu_, dn_p, nd_, mask))
+        lu = nu_ if up is not None else len(design_oversampling_filter(factor, self.lib))
+        ld = nd_ if down is not None else len(design_oversampling_filter(factor, self.lib))
+        self._os = (int(factor), lu, ld)
+        return self
+
+    @property
+    def oversampling(self):
+        """the batch's oversampling factor (1: off)"""
+        return self._os[0]
+
+    @property
+    def oversampling_delay(self):
+        """base-rate samples by which the interpolation and decimation filters delay the signal (linear-phase filters:
+        ((Lu - 1) + (Ld - 1)) / (2 factor); the default pair: the whole number (L - 1) / factor); 0 without oversampling"""
+        k, lu, ld = self._os
+        if k == 1:
+            return 0
+        d = ((lu - 1) + (ld - 1)) / (2 * k)
+        return int(d) if d == int(d) else d
 
     def set_balance(self, mode=-1):
         """Placement of the waves by their measured cost (``acme_batch_set_balance``): -1 the library decides
@@ -607,6 +664,13 @@ class MultiDeviceRunner:
                 self.runners.append(ModelRunner(model, hi - lo, device=dev, lib=self.lib, models=part))
             else:
                 self.runners.append(None)
+
+    def set_oversampling(self, factor, up=None, down=None, held_rows=()):
+        """``ModelRunner.set_oversampling`` on every device's batch"""
+        for r in self.runners:
+            if r is not None:
+                r.set_oversampling(factor, up, down, held_rows)
+        return self
 
     def run(self, u, y=None, check=True):
         """``u``: (N, T, nu) C-contiguous float64 (the ABI's layout); returns / fills ``y`` (N, T, ny)."""

@@ -197,6 +197,37 @@ int acme_batch_release_host_buffers(acme_batch *b);
 typedef void (*acme_progress_fn)(void *user, long long samples_done, long long samples_total);
 int acme_batch_set_progress_callback(acme_batch *b, acme_progress_fn fn, void *user);
 
+/* Oversampled runs.  A nonlinear model run at the audio rate fs aliases its own harmonics back into the audio band, so
+ * models are derived at k fs.  A batch with a factor k (1 ... ACME_MAX_OVERSAMPLING) takes u [N][T][nu] and returns
+ * y [N][T][ny] at the BASE rate fs through every run entry point (acme_batch_run, _run_const, _run_async; host and device
+ * memory) while its model -- the caller's DiscreteModel, derived at k fs -- advances k T samples:
+ *   interpolation  for each input row that is not held: s[m] = u[m/k] if k divides m, else 0;
+ *                  u_os[m] = sum_{j=0}^{Lu-1} g[j] s[m-j]  with g = k h_up (the library multiplies by k once, on the host)
+ *   held rows      u_os[m] = u[floor(m/k)] (zero-order hold): the rows of the mask held_rows -- pot positions, supplies, mix
+ *                  controls -- and the constant rows of acme_batch_run_const, always
+ *   decimation     y[n] = sum_{j=0}^{Ld-1} h_down[j] y_os[n k + k - 1 - j]
+ * Every sum runs over ascending j as a chain of fma: results are bit-identical across host and device memory, time slices
+ * and split calls.  Before the first run after the factor is set, each signal extends its first value into the past
+ * (u[n < 0] = u[0], y_os[m < 0] = y_os[0]: a DC input, or an instance set to its steady state, starts without a filter
+ * transient); from then on the histories are carried from call to call (T1 then T2 samples = one run of T1 + T2, bit for
+ * bit).  acme_batch_set_matrices zeroes the histories of the instances it makes afresh; acme_batch_set_state leaves them
+ * alone.  COUNTERS: acme_report counts model-rate samples (first_nonconverged / first_nonfinite are model-rate indices,
+ * k n + phase); the progress callback counts base-rate samples.
+ * Runs go slice by slice on the launch stream (interpolate, the unchanged run kernel over k x the slice, decimate; bounded
+ * scratch); host buffers take the sliced copy pipeline, never the streamed path of acme_batch_set_host_retention.  Not
+ * together with acme_batch_set_isolation (ACME_ERR_UNSUPPORTED either way round). */
+#define ACME_MAX_OVERSAMPLING 16
+/* the library's default lowpass for `factor`: a linear-phase Kaiser-windowed sinc at the high rate, unit DC gain, passband
+ * to 0.40 fs (ripple below 1e-4), at least 80 dB from 0.50 fs; length L odd and L = 1 (mod factor), so the pair delays the
+ * signal by the whole number (L - 1) / factor of base-rate samples.  Returns L (or a negative error code) and writes the taps
+ * when capacity >= L.  Factor 1: the single tap 1. */
+int acme_oversampling_design(int factor, double *taps, int capacity);
+/* set the batch's factor (1 switches oversampling off: today's path, none of the resampling runs) and filters: h_up /
+ * h_down with n_up / n_down (1 ... 4096) taps, NULL = the default design; held_rows bit r = input row r held.  Validates
+ * its arguments (ACME_ERR_INVALID) and resets the histories. */
+int acme_batch_set_oversampling(acme_batch *b, int factor, const double *h_up, int n_up, const double *h_down, int n_down,
+                                unsigned long long held_rows);
+
 /* acme_batch_run without blocking the caller: the same run on a worker thread of the library (a
  * host-buffer run drives its time-slice pipeline from there).  ONE host thread can thereby keep one
  * batch per GPU of a node busy -- start all, then acme_batch_wait each -- which is how a single

@@ -44,6 +44,7 @@ const ACME_KIND_MOSFET, ACME_KIND_MACAK, ACME_KIND_JA = Cint(4), Cint(5), Cint(6
 const ACME_MAX_ELEM_PAR = 16
 const ACME_SOLVER_SIMPLE, ACME_SOLVER_HOMOTOPY, ACME_SOLVER_CACHING_HOMOTOPY = Cint(0), Cint(1), Cint(2)
 const ACME_MEM_HOST, ACME_MEM_DEVICE = Cint(0), Cint(1)
+const ACME_MAX_OVERSAMPLING = 16
 const KIND_NQ = Dict(1 => 2, 2 => 4, 3 => 5, 4 => 3, 5 => 2, 6 => 4)
 const KIND_NN = Dict(1 => 1, 2 => 2, 3 => 2, 4 => 1, 5 => 1, 6 => 1)
 
@@ -272,6 +273,46 @@ What an instance computes does not depend on it.
 """
 set_balance!(r::BatchRunner, mode::Integer) =
     (check(ccall((:acme_batch_set_balance, lib), Cint, (Ptr{Cvoid}, Cint), r.h, mode)); r)
+
+"""
+    oversampling_design(factor) -> Vector{Float64}
+
+The library's default lowpass for oversampling by `factor` (`acme_oversampling_design`): linear-phase Kaiser-windowed
+sinc at the high rate, unit DC gain, passband to 0.40 fs, at least 80 dB from 0.50 fs, length L odd with L = 1 (mod
+factor) -- the pair delays the signal by (L - 1) / factor base-rate samples.  Python and Julia get the same taps.
+"""
+function oversampling_design(factor::Integer)
+    n = check(ccall((:acme_oversampling_design, lib), Cint, (Cint, Ptr{Cdouble}, Cint), factor, C_NULL, 0))
+    taps = zeros(Float64, n)
+    check(ccall((:acme_oversampling_design, lib), Cint, (Cint, Ptr{Cdouble}, Cint), factor, taps, n))
+    return taps
+end
+
+"""
+    set_oversampling!(runner, factor; up=nothing, down=nothing, held_rows=())
+
+Oversampled runs (`acme_batch_set_oversampling`): the runner's model is derived at `factor` x the signal rate; `run!`
+then takes `u` and returns `y` at the BASE rate while the model advances `factor` samples per column.  Input rows are
+interpolated with `factor * up`, the rows in `held_rows` (1-based: pot positions, supplies, mix controls) held, the
+outputs decimated with `down`; `nothing` = the library's default lowpass (`oversampling_design`).  Resets the filters'
+histories: each signal's first column extends into the past at the next `run!`, later calls continue where the last
+ended.  Reports count model-rate samples.  `factor = 1` switches it off.
+"""
+function set_oversampling!(r::BatchRunner, factor::Integer; up=nothing, down=nothing, held_rows=())
+    nu = ACME.nu(r.model)
+    mask = UInt64(0)
+    for k in held_rows
+        1 <= k <= min(nu, 64) || throw(DimensionMismatch("held row $k of a model with $nu inputs"))
+        mask |= UInt64(1) << (k - 1)
+    end
+    hu = up === nothing ? Float64[] : collect(Float64, up)
+    hd = down === nothing ? Float64[] : collect(Float64, down)
+    GC.@preserve hu hd check(ccall((:acme_batch_set_oversampling, lib), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Culonglong),
+                r.h, factor, up === nothing ? Ptr{Cdouble}(C_NULL) : pointer(hu), length(hu),
+                down === nothing ? Ptr{Cdouble}(C_NULL) : pointer(hd), length(hd), mask))
+    return r
+end
 
 """
     set_models!(runner, first, models)
