@@ -2,6 +2,7 @@
 // backend `be::` so that the HIP library (acme_hip.hip) and the CPU wave emulator used by the
 // GPU-less unit tests (tests/emu) share every line of host logic.  Included, not compiled alone.
 #include "acme_resample.h"
+#include "acme_measure.h"
 // ------------------------------------------------------------------------------------------
 // handles
 // ------------------------------------------------------------------------------------------
@@ -134,6 +135,19 @@ struct acme_batch {
         size_t cap_ou = 0, cap_oy = 0, cap_base = 0;
         be::event_t ev[2] = {};                  // host-buffer runs: slice s has been decimated
     } os;
+    // Output measurements (acme_batch_set_measurement, acme_measure.h): accumulators per instance and measured row, fed
+    // slice by slice from the base-rate outputs of every run while armed (run_os)
+    struct Measurement {
+        bool on = false;
+        long long start = 0, length = 0, f_num = 0, f_den = 1;
+        int H = 0, nrows = 0;
+        unsigned char row[64] = {};              // the measured rows, ascending
+        long long pos = 0;                       // base-rate samples since arming
+        double *d_acc = nullptr;                 // [4 + 2H][N nrows]
+        double *d_tw = nullptr;                  // one chunk's twiddles, [H][MEAS_CHUNK] pairs
+        double *d_ys = nullptr;                  // y = NULL: one slice of base-rate outputs, [N][TS][ny]
+        size_t cap_ys = 0;
+    } meas;
     // acme_batch_run_async: the run in flight on a worker thread of the library, its status and message
     std::thread worker;
     int worker_rc = ACME_OK;
@@ -703,6 +717,7 @@ void acme_batch_destroy(acme_batch *b) {
     (void)be::flag_free(b->h_u_ready);
     (void)be::dfree(b->os.d_taps); (void)be::dfree(b->os.d_hist_u); (void)be::dfree(b->os.d_hist_y);
     (void)be::dfree(b->os.d_ou); (void)be::dfree(b->os.d_oy); (void)be::dfree(b->os.d_base);
+    (void)be::dfree(b->meas.d_acc); (void)be::dfree(b->meas.d_tw); (void)be::dfree(b->meas.d_ys);
     for (auto &e : b->os.ev) if (e) (void)be::event_destroy(e);
     for (int i = 0; i < acme_batch::NEV; ++i) {
         if (b->ev0[i]) (void)be::event_destroy(b->ev0[i]);
@@ -825,6 +840,7 @@ static int rebuild_on_plain_shape(acme_batch *b) {
     nb->iso_thr = b->iso_thr;
     nb->balance = b->balance;
     std::swap(nb->os, b->os);    // (oversampling: factor, taps, the signals' past and scratch go with the instances)
+    std::swap(nb->meas, b->meas);    // (measurements: the window's position and the accumulators, too)
     std::swap(*b, *nb);          // (b is the plain-shape batch now; the guard destroys what it was)
     return ACME_OK;
 }
@@ -1200,12 +1216,16 @@ static bool streamed_fits(const acme_batch *b) {
     return blocks <= per_cu * cus;
 }
 
-// ---- oversampled runs (acme_batch_set_oversampling) -----------------------------------------------------------------------
+// ---- oversampled runs (acme_batch_set_oversampling) and measured runs (acme_batch_set_measurement) ----------------------
 // Time slice by time slice on the launch stream: [put the full input rows together (run_const)] -> interpolate to the model
-// rate (acme_resample.h) -> the UNCHANGED run kernel over k x the slice's samples -> decimate; the histories carry the
-// signals' past from slice to slice and call to call.  The model-rate scratch is one slice's (ACME_OS_SLICE base-rate
-// samples, default 4 096: config 5 -- 2 048 instances at k = 4 -- 0.8 GB).  Host buffers: the staged pipeline of run_impl, two
-// staging buffers each way, the copies of slices s + 1 (in) and s - 1 (out) beside slice s; never the streamed path.
+// rate (acme_resample.h) -> the UNCHANGED run kernel over k x the slice's samples -> decimate -> [measure the slice's
+// base-rate outputs (acme_measure.h)]; the histories carry the signals' past from slice to slice and call to call.  The
+// model-rate scratch is one slice's (ACME_OS_SLICE base-rate samples, default 4 096: config 5 -- 2 048 instances at k = 4 --
+// 0.8 GB).  Host buffers: the staged pipeline of run_impl, two staging buffers each way, the copies of slices s + 1 (in) and
+// s - 1 (out) beside slice s; never the streamed path.
+// k = 1 (a measurement without oversampling): there is nothing to resample -- the run kernel reads the slice's input rows and
+// writes its outputs where the measurement reads them.  Device arrays with y stored run as ONE slice, the launch a plain run
+// makes; y = NULL: outputs go to one slice of scratch (meas.d_ys) and are never copied anywhere.
 static long long os_slice(long long T) {
     long long TS = 4096;
     if (const char *e = getenv("ACME_OS_SLICE")) { const long long v = atoll(e); if (v >= 1) TS = v; }
@@ -1219,21 +1239,43 @@ static int os_grow(double **p, size_t *cap, size_t bytes) {
     }
     return ACME_OK;
 }
-// u: [N][T][nu], or -- const_mask != 0 -- the varying rows [N][T][nuv] and u_const [N][nu] (acme_batch_run_const)
+// the measurement step of n base-rate output samples (instance i, sample t, row r at y[(i * pitch + t) * ny + r]) that follow
+// the meas.pos samples since arming: the part inside the window [start, start + length), chunk by chunk
+static int meas_step(acme_batch *b, const double *y, long long n, long long pitch, be::stream_t st) {
+    acme_batch::Measurement &M = b->meas;
+    const long long end = M.length ? M.start + M.length : LLONG_MAX;
+    const long long lo = M.pos > M.start ? M.pos : M.start, hi = M.pos + n < end ? M.pos + n : end;
+    for (long long s = lo; M.nrows > 0 && s < hi; s += MEAS_CHUNK) {
+        const long long len = hi - s < MEAS_CHUNK ? hi - s : MEAS_CHUNK;
+        const MeasTwArgs W{M.d_tw, s - M.start, len, M.f_num, M.f_den, M.H};
+        MeasArgs A{y, M.d_acc, M.d_tw, b->N, len, pitch, s - M.pos, b->P.actual.ny, M.nrows, M.H, {}};
+        memcpy(A.row, M.row, sizeof(A.row));
+        HIPCHK(meas_launch(W, A, st));
+    }
+    M.pos += n;
+    return ACME_OK;
+}
+// u: [N][T][nu], or -- const_mask != 0 -- the varying rows [N][T][nuv] and u_const [N][nu] (acme_batch_run_const); y: [N][T][ny],
+// or NULL (a measured run that stores no outputs)
 static int run_os(acme_batch *b, const double *u, const double *u_const, unsigned long long const_mask, double *y, long long T,
                   int mem, be::stream_t st) {
     acme_batch::Oversampling &O = b->os;
+    acme_batch::Measurement &M = b->meas;
     const int k = O.k, nu = b->P.actual.nu, ny = b->P.actual.ny;
     const size_t N = (size_t)b->N;
     int nin = nu;                               // rows of u as the caller hands them over
     for (int r = 0; r < nu && r < 64; ++r) nin -= (const_mask >> r & 1ull) ? 1 : 0;
-    const bool host = mem == ACME_MEM_HOST, expand = const_mask != 0ull;
-    const long long TS = os_slice(T), ns = (T + TS - 1) / TS;
+    const bool host = mem == ACME_MEM_HOST, expand = const_mask != 0ull, keep = y != nullptr;
+    const long long TS = k == 1 && !host && keep ? T : os_slice(T), ns = (T + TS - 1) / TS;
     auto len = [&](long long s) { return (s + 1) * TS <= T ? TS : T - s * TS; };
-    int rc = os_grow(&O.d_ou, &O.cap_ou, sizeof(double) * N * (size_t)(k * TS) * nu);
-    if (rc == ACME_OK) rc = os_grow(&O.d_oy, &O.cap_oy, sizeof(double) * N * (size_t)(k * TS) * ny);
-    if (rc == ACME_OK && expand) rc = os_grow(&O.d_base, &O.cap_base, sizeof(double) * N * (size_t)TS * nu);
-    if (rc == ACME_OK && host) rc = ensure_staging(b, 2 * sizeof(double) * N * (size_t)TS * nin, 2 * sizeof(double) * N * (size_t)TS * ny);
+    // (k = 1: the slices of caller's device arrays are packed into d_base when they are not whole)
+    const bool pack = k == 1 && !host && !expand && nu && ns > 1;
+    int rc = ACME_OK;
+    if (k > 1) rc = os_grow(&O.d_ou, &O.cap_ou, sizeof(double) * N * (size_t)(k * TS) * nu);
+    if (rc == ACME_OK && k > 1) rc = os_grow(&O.d_oy, &O.cap_oy, sizeof(double) * N * (size_t)(k * TS) * ny);
+    if (rc == ACME_OK && (expand || pack)) rc = os_grow(&O.d_base, &O.cap_base, sizeof(double) * N * (size_t)TS * nu);
+    if (rc == ACME_OK && !keep) rc = os_grow(&M.d_ys, &M.cap_ys, sizeof(double) * N * (size_t)TS * ny);
+    if (rc == ACME_OK && host) rc = ensure_staging(b, 2 * sizeof(double) * N * (size_t)TS * nin, keep ? 2 * sizeof(double) * N * (size_t)TS * ny : 0);
     if (rc == ACME_OK && host && expand) rc = os_grow(&b->d_uc, &b->cap_uc, sizeof(double) * N * (size_t)nu);
     if (rc != ACME_OK) return rc;
     const double *uc = u_const;
@@ -1249,30 +1291,37 @@ static int run_os(acme_batch *b, const double *u, const double *u_const, unsigne
         const long long n = len(s), nk = n * k;
         const double *src = host ? ubuf(s) : u + (size_t)s * TS * nin;
         long long pitch = host ? n : T;
-        if (expand) {
-            HIPCHK(be::launch_expand(O.d_base, src, uc, const_mask, (long long)N, n, pitch, nu, nin, st));
+        if (expand || pack) {
+            HIPCHK(be::launch_expand(O.d_base, src, expand ? uc : src, const_mask, (long long)N, n, pitch, nu, nin, st));
             src = O.d_base;
             pitch = n;
         }
-        if (nu) {
-            OsHistArgs H{O.d_hist_u, src, (long long)N, n, pitch, nu, O.du};
-            if (O.fresh) HIPCHK(os_launch_hist(H, true, st));
-            const OsInterpArgs I{src, O.d_hist_u, O.d_ou, g, (long long)N, n, pitch, nu, O.lu, O.du, O.held | const_mask};
-            HIPCHK(os_launch_interp(k, I, st));
-            HIPCHK(os_launch_hist(H, false, st));
+        // the slice's base-rate outputs
+        double *dst = !keep ? M.d_ys : host ? ybuf(s) : y + (size_t)s * TS * ny;
+        const long long ypitch = keep && !host ? T : n;
+        if (k == 1) {
+            const int rc_ = launch_run(b, src, dst, n, st, nullptr);
+            if (rc_ != ACME_OK) return rc_;
+        } else {
+            if (nu) {
+                OsHistArgs H{O.d_hist_u, src, (long long)N, n, pitch, nu, O.du};
+                if (O.fresh) HIPCHK(os_launch_hist(H, true, st));
+                const OsInterpArgs I{src, O.d_hist_u, O.d_ou, g, (long long)N, n, pitch, nu, O.lu, O.du, O.held | const_mask};
+                HIPCHK(os_launch_interp(k, I, st));
+                HIPCHK(os_launch_hist(H, false, st));
+            }
+            const int rc_ = launch_run(b, O.d_ou, O.d_oy, nk, st, nullptr);
+            if (rc_ != ACME_OK) return rc_;
+            if (ny) {
+                OsHistArgs H{O.d_hist_y, O.d_oy, (long long)N, nk, nk, ny, O.ld - 1};
+                if (O.fresh) HIPCHK(os_launch_hist(H, true, st));
+                const OsDecimArgs D{O.d_oy, O.d_hist_y, dst, h, (long long)N, n, ypitch, k, ny, O.ld};
+                HIPCHK(os_launch_decim(D, st));
+                HIPCHK(os_launch_hist(H, false, st));
+            }
+            O.fresh = false;
         }
-        const int rc_ = launch_run(b, O.d_ou, O.d_oy, nk, st, nullptr);
-        if (rc_ != ACME_OK) return rc_;
-        if (ny) {
-            OsHistArgs H{O.d_hist_y, O.d_oy, (long long)N, nk, nk, ny, O.ld - 1};
-            if (O.fresh) HIPCHK(os_launch_hist(H, true, st));
-            double *dst = host ? ybuf(s) : y + (size_t)s * TS * ny;
-            const OsDecimArgs D{O.d_oy, O.d_hist_y, dst, h, (long long)N, n, host ? n : T, k, ny, O.ld};
-            HIPCHK(os_launch_decim(D, st));
-            HIPCHK(os_launch_hist(H, false, st));
-        }
-        O.fresh = false;
-        return ACME_OK;
+        return M.on ? meas_step(b, dst, n, ypitch, st) : ACME_OK;
     };
     if (!host) {
         for (long long s = 0; s < ns; ++s) {
@@ -1285,7 +1334,7 @@ static int run_os(acme_batch *b, const double *u, const double *u_const, unsigne
     if (!b->retain_host) { release_reg(b->reg_u); release_reg(b->reg_y); }
     else {
         (void)ensure_registered(b->reg_u, u, sizeof(double) * N * (size_t)T * (nin ? nin : 1));
-        (void)ensure_registered(b->reg_y, y, sizeof(double) * N * (size_t)T * ny);
+        if (keep) (void)ensure_registered(b->reg_y, y, sizeof(double) * N * (size_t)T * ny);
     }
     if (!b->copy_stream) HIPCHK(be::stream_create_nonblocking(&b->copy_stream));
     if (!b->copy_stream_out) HIPCHK(be::stream_create_nonblocking(&b->copy_stream_out));
@@ -1296,7 +1345,7 @@ static int run_os(acme_batch *b, const double *u, const double *u_const, unsigne
         return be::copy2d_h2d_async(ubuf(s), w, u + (size_t)s * TS * nin, sizeof(double) * (size_t)T * nin, w, N, cs);
     };
     auto copy_out = [&](long long s) -> int {
-        if (!ny) return 0;
+        if (!ny || !keep) return 0;
         const size_t w = sizeof(double) * (size_t)len(s) * ny;
         return be::copy2d_d2h_async(y + (size_t)s * TS * ny, sizeof(double) * (size_t)T * ny, ybuf(s), w, w, N, cso);
     };
@@ -1306,7 +1355,7 @@ static int run_os(acme_batch *b, const double *u, const double *u_const, unsigne
         rc = slice(s);
         if (rc != ACME_OK) return rc;
         HIPCHK(be::event_record(O.ev[s & 1], st));
-        if (s > 0) HIPCHK(be::event_sync(O.ev[(s - 1) & 1]));       // slice s-1 decimated: its buffers are free
+        if (s > 0) HIPCHK(be::event_sync(O.ev[(s - 1) & 1]));       // slice s-1 done: its buffers are free
         if (s + 1 < ns) HIPCHK(copy_in(s + 1));                      // both overlap slice s, and each other
         if (s > 0) HIPCHK(copy_out(s - 1));
         if (s + 1 < ns) HIPCHK(be::stream_sync(cs));
@@ -1330,11 +1379,12 @@ int acme_batch_run(acme_batch *b, const double *u, double *y, long long T, int m
 static int run_impl(acme_batch *b, const double *u, double *y, long long T, int mem, void *stream) {
     if (!b || T < 0) return fail(ACME_ERR_INVALID, "invalid argument to acme_batch_run");
     const int nu = b->P.actual.nu, ny = b->P.actual.ny;
-    if ((nu > 0 && T > 0 && !u) || (ny > 0 && T > 0 && !y)) return fail(ACME_ERR_INVALID, "null u or y");
+    // (y = NULL: a measured run that stores no outputs -- only while a measurement is armed)
+    if ((nu > 0 && T > 0 && !u) || (ny > 0 && T > 0 && !y && !b->meas.on)) return fail(ACME_ERR_INVALID, "null u or y");
     if (T == 0) return ACME_OK;
     ON_DEVICE(b);
     be::stream_t st = (be::stream_t)stream;
-    if (b->os.k > 1) {
+    if (b->os.k > 1 || b->meas.on) {
         if (mem != ACME_MEM_HOST && mem != ACME_MEM_DEVICE) return fail(ACME_ERR_INVALID, "mem must be ACME_MEM_HOST or ACME_MEM_DEVICE");
         return run_os(b, u, nullptr, 0ull, y, T, mem, st);
     }
@@ -1564,12 +1614,12 @@ int acme_batch_run_const(acme_batch *b, const double *u_var, const double *u_con
     int nuv = 0;
     for (int k = 0; k < nu; ++k) nuv += (const_mask >> k & 1ull) ? 0 : 1;
     if (const_mask == 0ull) return run_impl(b, u_var, y, T, mem, stream);
-    if ((nuv > 0 && T > 0 && !u_var) || !u_const || (ny > 0 && T > 0 && !y)) return fail(ACME_ERR_INVALID, "null u_var, u_const or y");
+    if ((nuv > 0 && T > 0 && !u_var) || !u_const || (ny > 0 && T > 0 && !y && !b->meas.on)) return fail(ACME_ERR_INVALID, "null u_var, u_const or y");
     if (mem != ACME_MEM_HOST && mem != ACME_MEM_DEVICE) return fail(ACME_ERR_INVALID, "mem must be ACME_MEM_HOST or ACME_MEM_DEVICE");
     if (T == 0) return ACME_OK;
     ON_DEVICE(b);
     be::stream_t st = (be::stream_t)stream;
-    if (b->os.k > 1) return run_os(b, u_var, u_const, const_mask, y, T, mem, st);
+    if (b->os.k > 1 || b->meas.on) return run_os(b, u_var, u_const, const_mask, y, T, mem, st);
     const size_t N = (size_t)b->N;
     auto grow = [&](double **p, size_t *cap, size_t bytes) -> int {
         if (bytes > *cap) {
@@ -1702,6 +1752,8 @@ int acme_batch_set_isolation(acme_batch *b, double iters_per_sample) {
     if (!b || !(iters_per_sample >= 0.0)) return fail(ACME_ERR_INVALID, "invalid argument to acme_batch_set_isolation");
     if (iters_per_sample > 0.0 && b->os.k > 1)
         return fail(ACME_ERR_UNSUPPORTED, "isolation of slow instances is not available on an oversampled batch");
+    if (iters_per_sample > 0.0 && b->meas.on)
+        return fail(ACME_ERR_UNSUPPORTED, "isolation of slow instances is not available while a measurement is armed");
     ON_DEVICE(b);
     HIPCHK(be::device_sync());
     b->iso_thr = iters_per_sample;
@@ -1756,6 +1808,109 @@ int acme_batch_set_oversampling(acme_batch *b, int factor, const double *h_up, i
     HIPCHK(be::dmalloc((void **)&O.d_hist_y, sizeof(double) * (size_t)b->N * (size_t)(O.ld - 1) * ny));
     for (auto &e : O.ev) if (!e) HIPCHK(be::event_create(&e));
     O.k = factor;
+    return ACME_OK;
+}
+
+// the accumulators' start values and the window's start (acme_batch_set_measurement / _reset_measurement)
+static int meas_zero(acme_batch *b) {
+    acme_batch::Measurement &M = b->meas;
+    const size_t P = (size_t)b->N * M.nrows;
+    std::vector<double> a((size_t)(4 + 2 * M.H) * P);
+    for (int k = 0; k < 4 + 2 * M.H; ++k)
+        for (size_t p = 0; p < P; ++p) a[k * P + p] = meas_init(k);
+    if (!a.empty()) HIPCHK(be::copy_h2d(M.d_acc, a.data(), sizeof(double) * a.size()));
+    M.pos = 0;
+    return ACME_OK;
+}
+
+// spec = nullptr: off
+struct MeasSpec { long long start, length, f_num, f_den; int harmonics; unsigned long long rows; };
+static int set_measurement(acme_batch *b, const MeasSpec *spec) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const int ny = b->P.actual.ny;
+    int nrows = 0;
+    unsigned char row[64] = {};
+    if (spec) {
+        if (spec->start < 0 || spec->length < 0 || (spec->length > 0 && spec->length > LLONG_MAX - spec->start))
+            return fail(ACME_ERR_INVALID, "measurement window: start and length must be >= 0");
+        if (spec->f_den <= 0 || spec->f_den >= (1ll << 31)) return fail(ACME_ERR_INVALID, "measurement: f_den must be 1 ... 2^31 - 1");
+        if (spec->harmonics < 0 || spec->harmonics > MEAS_MAX_H) return fail(ACME_ERR_INVALID, "measurement: harmonics must be 0 ... 32");
+        if (spec->rows == 0ull && ny > 64) return fail(ACME_ERR_INVALID, "measurement: name the rows of a model with more than 64 outputs");
+        if (ny < 64 && (spec->rows >> ny) != 0ull) return fail(ACME_ERR_INVALID, "measurement: row beyond the model's outputs");
+        const unsigned long long rows = spec->rows ? spec->rows : ny >= 64 ? ~0ull : ((1ull << ny) - 1ull);
+        for (int r = 0; r < 64 && r < ny; ++r)
+            if (rows >> r & 1ull) row[nrows++] = (unsigned char)r;
+        if (b->iso_thr > 0.0)
+            return fail(ACME_ERR_UNSUPPORTED, "measurements are not available while the isolation of slow instances is in force");
+    }
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());          // (a launch still in flight may write the accumulators)
+    acme_batch::Measurement &M = b->meas;
+    (void)be::dfree(M.d_acc); (void)be::dfree(M.d_tw); (void)be::dfree(M.d_ys);
+    M = acme_batch::Measurement{};
+    if (!spec) return ACME_OK;
+    M.start = spec->start;
+    M.length = spec->length;
+    M.f_den = spec->f_den;
+    M.f_num = spec->f_num % spec->f_den;
+    if (M.f_num < 0) M.f_num += M.f_den;
+    M.H = spec->harmonics;
+    M.nrows = nrows;
+    memcpy(M.row, row, sizeof(row));
+    HIPCHK(be::dmalloc((void **)&M.d_acc, sizeof(double) * (size_t)(4 + 2 * M.H) * (size_t)b->N * nrows));
+    HIPCHK(be::dmalloc((void **)&M.d_tw, sizeof(double) * 2 * (size_t)M.H * MEAS_CHUNK));
+    for (auto &e : b->os.ev) if (!e) HIPCHK(be::event_create(&e));      // (the host pipeline of run_os)
+    const int rc = meas_zero(b);
+    if (rc != ACME_OK) return rc;
+    M.on = true;
+    return ACME_OK;
+}
+
+int acme_batch_set_measurement(acme_batch *b, long long start, long long length, long long f_num, long long f_den,
+                               int harmonics, unsigned long long rows) {
+    const MeasSpec spec{start, length, f_num, f_den, harmonics, rows};
+    return set_measurement(b, &spec);
+}
+
+int acme_batch_clear_measurement(acme_batch *b) { return set_measurement(b, nullptr); }
+
+int acme_batch_reset_measurement(acme_batch *b) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    if (!b->meas.on) return fail(ACME_ERR_INVALID, "no measurement is armed");
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    return meas_zero(b);
+}
+
+int acme_batch_get_measurement(acme_batch *b, double *out, long long *count) {
+    join_worker(b);
+    if (!b || (!out && !count)) return fail(ACME_ERR_INVALID, "null argument");
+    const acme_batch::Measurement &M = b->meas;
+    if (!M.on) return fail(ACME_ERR_INVALID, "no measurement is armed");
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    const long long end = M.length ? M.start + M.length : LLONG_MAX;
+    const long long cnt = (M.pos < end ? M.pos : end) - M.start;
+    const long long c = cnt > 0 ? cnt : 0;
+    if (count) *count = c;
+    if (!out) return ACME_OK;
+    const size_t P = (size_t)b->N * M.nrows, W = (size_t)(4 + 2 * M.H);
+    std::vector<double> a(W * P);
+    if (!a.empty()) HIPCHK(be::copy_d2h(a.data(), M.d_acc, sizeof(double) * a.size()));
+    const double inv = 1.0 / (double)c;            // (no sample measured yet: NaN and infinities)
+    for (size_t p = 0; p < P; ++p) {
+        double *o = out + p * W;
+        o[0] = a[p] * inv;
+        o[1] = std::sqrt(a[P + p] * inv);
+        o[2] = a[2 * P + p];
+        o[3] = a[3 * P + p];
+        for (int h = 0; h < M.H; ++h) {            // A_h = (2 / count) (C_h - j S_h)
+            o[4 + 2 * h] = 2.0 * a[(4 + 2 * h) * P + p] * inv;
+            o[5 + 2 * h] = -2.0 * a[(5 + 2 * h) * P + p] * inv;
+        }
+    }
     return ACME_OK;
 }
 

@@ -1,0 +1,215 @@
+// acme_measure.h -- output measurements of a batch (acme_batch_set_measurement): per instance and measured output row the
+// library accumulates, over the samples of a window, the sum, the sum of squares, min, max and for h = 1 ... H the two
+// correlations of y with cos / sin of the h-th harmonic of the fundamental f = f_num / f_den x fs:
+//
+//   sum += y      sq = fma(y, y, sq)      min, max (NaN sticks)
+//   C_h = fma(y, cos th, C_h)   S_h = fma(y, sin th, S_h)   th = 2 pi ((h f_num m) mod f_den) / f_den,  m = n - start
+//
+// Each accumulator is ONE chain in sample order, and the phase is reduced exactly in 64-bit integers (meas_twiddle, shared
+// by host and device code): the result does not depend on where a slice or a call ends, on host or device memory, on the
+// entry point or on whether y is stored.  The accumulators live in HBM, [4 + 2H][N nrows] (pair p = i nrows + j: instance
+// i, j-th measured row), and carry from one slice to the next (acme_api.inc run_os: one step after the slice's run kernel
+// or decimation).
+//
+// A step covers one chunk of at most MEAS_CHUNK samples: a small kernel writes the chunk's twiddles, [H][len] pairs
+// (cos, sin) -- once per sample and harmonic, not per instance --, then the measurement kernel runs over the chunk.  Its
+// block takes 64 pairs (a lane each) and one wave per UNIT: unit 0 the four moments, unit h the harmonic h; the H + 1
+// units of a pair run side by side (grid.y splits them beyond 16 waves).  y is instance-major, so lanes that own
+// instances would read 64 rows apart at every sample: the block stages tiles of 64 pairs x 64 samples through LDS with
+// loads along the samples (contiguous per pair), and every wave then reads its lane's column.  A harmonic wave holds
+// 64 samples' twiddles in its lanes and broadcasts the current one (v_readlane: no memory access).
+//
+// The per-element functions are host + device code; the launchers below are __global__ launches under hipcc and plain
+// loops otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with g++).
+#pragma once
+#include <climits>
+#include <cmath>
+
+#include "acme_common.h"
+
+namespace acme {
+
+constexpr int MEAS_MAX_H = 32;
+constexpr long long MEAS_CHUNK = 4096;      // samples per measurement step (twiddle table: H x 4096 x 16 B at most)
+constexpr int MEAS_TILE = 64;               // samples per LDS tile
+constexpr int MEAS_MAX_WAVES = 16;          // waves (units) per block
+
+struct MeasArgs {
+    const double *y;            // instance i, sample t, row r at y[(i * pitch + t0 + t) * ny + r]
+    double *acc;                // [4 + 2H][n * nrows]
+    const double *tw;           // [H][len] pairs (cos, sin)
+    long long n, len, pitch, t0;
+    int ny, nrows, H;
+    unsigned char row[64];      // the measured rows, ascending
+};
+
+struct MeasTwArgs {
+    double *tw;                 // [H][len] pairs (cos, sin) of samples m0 ... m0 + len - 1 (window-relative)
+    long long m0, len, f_num, f_den;    // 0 <= f_num < f_den < 2^31
+    int H;
+};
+
+// cos / sin of 2 pi ((h f_num m) mod f_den) / f_den, the phase reduced exactly (h <= 32, f_den < 2^31: products < 2^62)
+// and taken to (-pi, pi] before the one rounding of the angle
+ACME_HD inline void meas_twiddle(long long h, long long m, long long f_num, long long f_den, double *c, double *s) {
+    const long long a = (h * f_num) % f_den;
+    long long k = (a * (m % f_den)) % f_den;
+    if (2 * k > f_den) k -= f_den;
+    const double th = 6.283185307179586476925286766559 * ((double)k / (double)f_den);
+    *c = cos(th);
+    *s = sin(th);
+}
+
+ACME_HD inline void meas_tw(const MeasTwArgs &A, long long idx) {
+    const long long h = idx / A.len, t = idx - h * A.len;
+    meas_twiddle(h + 1, A.m0 + t, A.f_num, A.f_den, &A.tw[2 * idx], &A.tw[2 * idx + 1]);
+}
+
+// NaN sticks: once an accumulator is NaN it stays so
+ACME_HD inline double meas_min(double m, double v) { return (v < m || v != v) ? v : m; }
+ACME_HD inline double meas_max(double m, double v) { return (v > m || v != v) ? v : m; }
+
+// the accumulators' start values: sum, sq 0; min +inf; max -inf; C_h, S_h 0
+inline double meas_init(int a) { return a == 2 ? INFINITY : a == 3 ? -INFINITY : 0.0; }
+
+// one unit of one pair over the chunk, sample after sample (the reference order every backend keeps)
+ACME_HD inline void meas_chain(const MeasArgs &A, long long p, int u) {
+    const long long P = A.n * A.nrows;
+    const long long i = p / A.nrows;
+    const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    double *acc = A.acc + p;
+    if (u == 0) {
+        double s = acc[0], q = acc[P], mn = acc[2 * P], mx = acc[3 * P];
+        for (long long t = 0; t < A.len; ++t) {
+            const double v = yp[t * A.ny];
+            s += v;
+            q = fma(v, v, q);
+            mn = meas_min(mn, v);
+            mx = meas_max(mx, v);
+        }
+        acc[0] = s; acc[P] = q; acc[2 * P] = mn; acc[3 * P] = mx;
+        return;
+    }
+    const double *tw = A.tw + 2 * (u - 1) * A.len;
+    double c = acc[(2 + 2 * u) * P], sn = acc[(3 + 2 * u) * P];
+    for (long long t = 0; t < A.len; ++t) {
+        const double v = yp[t * A.ny];
+        c = fma(v, tw[2 * t], c);
+        sn = fma(v, tw[2 * t + 1], sn);
+    }
+    acc[(2 + 2 * u) * P] = c;
+    acc[(3 + 2 * u) * P] = sn;
+}
+
+// waves per block and blocks along y for H harmonics: H + 1 units, at most MEAS_MAX_WAVES waves a block
+inline void meas_shape(int H, int *waves, int *groups) {
+    const int U = H + 1;
+    *groups = (U + MEAS_MAX_WAVES - 1) / MEAS_MAX_WAVES;
+    *waves = (U + *groups - 1) / *groups;
+}
+
+}  // namespace acme
+
+// ---- launchers ---------------------------------------------------------------------------------------------------------
+#if defined(__HIPCC__)
+__global__ __launch_bounds__(256) void acme_meas_tw_kernel(acme::MeasTwArgs A) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx < A.H * A.len) acme::meas_tw(A, idx);
+}
+
+__device__ inline double acme_meas_bcast(double v, int l) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)b, l);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(b >> 32), l);
+    return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// block: 64 pairs x blockDim.x / 64 units (unit = blockIdx.y * waves + wave); every wave helps stage the tiles
+__global__ __launch_bounds__(1024) void acme_meas_kernel(acme::MeasArgs A) {
+    using namespace acme;
+    __shared__ double tile[64][MEAS_TILE + 1];          // [pair][sample]: column reads by lane hit distinct banks
+    __shared__ long long base[64];                      // a pair's first element of the chunk in y
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const long long P = A.n * A.nrows, p0 = (long long)blockIdx.x * 64, p = p0 + lane;
+    const int u = blockIdx.y * nw + w;
+    const bool mine = u <= A.H && p < P;
+    if (threadIdx.x < 64) {
+        const long long q = p0 + threadIdx.x;
+        if (q < P) {
+            const long long i = q / A.nrows;
+            base[threadIdx.x] = (i * A.pitch + A.t0) * A.ny + A.row[q - i * A.nrows];
+        }
+    }
+    // the unit's accumulators (unit 0: sum, sq, min, max; unit h: C_h, S_h)
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    const int ia = u == 0 ? 0 : 2 + 2 * u;
+    if (mine) {
+        a0 = A.acc[ia * P + p];
+        a1 = A.acc[(ia + 1) * P + p];
+        if (u == 0) { a2 = A.acc[2 * P + p]; a3 = A.acc[3 * P + p]; }
+    }
+    const double *tw = A.tw + 2 * (long long)(u > 0 ? u - 1 : 0) * A.len;
+    for (long long tb = 0; tb < A.len; tb += MEAS_TILE) {
+        const int nt = (int)(A.len - tb < MEAS_TILE ? A.len - tb : MEAS_TILE);
+        __syncthreads();                                // (the previous tile has been read by every wave)
+        for (int pp = w; pp < 64; pp += nw)            // wave pp: pair pp's samples, one per lane -- contiguous for ny = 1
+            if (p0 + pp < P && lane < nt) tile[pp][lane] = A.y[base[pp] + (tb + lane) * A.ny];
+        __syncthreads();
+        if (u > A.H) continue;
+        if (u == 0) {
+            for (int t = 0; t < nt; ++t) {
+                const double v = tile[lane][t];
+                a0 += v;
+                a1 = fma(v, v, a1);
+                a2 = meas_min(a2, v);
+                a3 = meas_max(a3, v);
+            }
+        } else {
+            double cl = 0.0, sl = 0.0;                 // lane t holds sample tb + t's twiddle
+            if (lane < nt) { cl = tw[2 * (tb + lane)]; sl = tw[2 * (tb + lane) + 1]; }
+            if (nt == MEAS_TILE) {                     // (a whole tile: a fixed trip count the compiler unrolls)
+#pragma unroll 8
+                for (int t = 0; t < MEAS_TILE; ++t) {
+                    const double v = tile[lane][t];
+                    a0 = fma(v, acme_meas_bcast(cl, t), a0);
+                    a1 = fma(v, acme_meas_bcast(sl, t), a1);
+                }
+            } else {
+                for (int t = 0; t < nt; ++t) {
+                    const double v = tile[lane][t];
+                    a0 = fma(v, acme_meas_bcast(cl, t), a0);
+                    a1 = fma(v, acme_meas_bcast(sl, t), a1);
+                }
+            }
+        }
+    }
+    if (mine) {
+        A.acc[ia * P + p] = a0;
+        A.acc[(ia + 1) * P + p] = a1;
+        if (u == 0) { A.acc[2 * P + p] = a2; A.acc[3 * P + p] = a3; }
+    }
+}
+namespace acme {
+inline int meas_launch(const MeasTwArgs &T, const MeasArgs &A, hipStream_t st) {
+    if (A.H > 0) {
+        hipLaunchKernelGGL(acme_meas_tw_kernel, dim3((unsigned)((A.H * A.len + 255) / 256)), dim3(256), 0, st, T);
+        const int e = (int)hipGetLastError();
+        if (e) return e;
+    }
+    int waves = 1, groups = 1;
+    meas_shape(A.H, &waves, &groups);
+    const long long P = A.n * A.nrows;
+    hipLaunchKernelGGL(acme_meas_kernel, dim3((unsigned)((P + 63) / 64), (unsigned)groups), dim3(64 * waves), 0, st, A);
+    return (int)hipGetLastError();
+}
+}  // namespace acme
+#else
+namespace acme {
+inline int meas_launch(const MeasTwArgs &T, const MeasArgs &A, void *) {
+    for (long long idx = 0; idx < A.H * A.len; ++idx) meas_tw(T, idx);
+    for (long long p = 0; p < A.n * A.nrows; ++p)
+        for (int u = 0; u <= A.H; ++u) meas_chain(A, p, u);
+    return 0;
+}
+}  // namespace acme
+#endif

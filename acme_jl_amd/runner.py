@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "acme_batch_solve", "acme_batch_get_extrapolation_jacobian", "acme_batch_last_kernel_ms", "acme_batch_kernel_time", "acme_batch_get_report", "acme_batch_reset_report",
     "acme_batch_set_resabstol", "acme_batch_get_state", "acme_batch_set_state",
     "acme_oversampling_design", "acme_batch_set_oversampling",
+    "acme_batch_set_measurement", "acme_batch_clear_measurement", "acme_batch_reset_measurement", "acme_batch_get_measurement",
 ]
 
 
@@ -138,6 +139,10 @@ class Library:
         L.acme_batch_set_state.argtypes = [vp, dp, dp, dp]
         L.acme_oversampling_design.argtypes = [C.c_int, dp, C.c_int]
         L.acme_batch_set_oversampling.argtypes = [vp, C.c_int, dp, C.c_int, dp, C.c_int, C.c_ulonglong]
+        L.acme_batch_set_measurement.argtypes = [vp, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, C.c_ulonglong]
+        L.acme_batch_clear_measurement.argtypes = [vp]
+        L.acme_batch_reset_measurement.argtypes = [vp]
+        L.acme_batch_get_measurement.argtypes = [vp, dp, C.POINTER(C.c_longlong)]
 
     def check(self, rc):
         if rc < 0:
@@ -171,6 +176,60 @@ def design_oversampling_filter(factor, lib=None):
     taps = np.zeros(n)
     lib.check(lib.L.acme_oversampling_design(int(factor), _dp(taps), n))
     return taps
+
+
+class Measurement:
+    """What ``ModelRunner.measurement()`` returns: per instance and measured output row (``rows``, ascending) the window's
+    ``mean``, ``rms``, ``min``, ``max`` and ``peak`` (N, nrows), and ``harmonics`` (N, nrows, H), the complex amplitudes
+    A_h = (2 / count) sum_m y[m] exp(-j h w m) of the fundamental's harmonics h = 1 ... H; ``count`` samples were measured."""
+
+    def __init__(self, out, count, rows):
+        self.count = int(count)
+        self.rows = tuple(rows)
+        self.mean, self.rms, self.min, self.max = (out[:, :, k].copy() for k in range(4))
+        self.harmonics = out[:, :, 4::2] + 1j * out[:, :, 5::2]
+
+    @property
+    def peak(self):
+        return np.maximum(np.abs(self.min), np.abs(self.max))
+
+    def thd(self):
+        """total harmonic distortion sqrt(sum_{h >= 2} |A_h|^2) / |A_1| (N, nrows); needs H >= 2"""
+        a = np.abs(self.harmonics)
+        if a.shape[2] < 2:
+            raise ValueError("THD needs a measurement of at least 2 harmonics")
+        return np.sqrt((a[:, :, 1:] ** 2).sum(axis=2)) / a[:, :, 0]
+
+    @classmethod
+    def concatenate(cls, parts):
+        m = cls.__new__(cls)
+        m.count, m.rows = parts[0].count, parts[0].rows
+        for k in ("mean", "rms", "min", "max", "harmonics"):
+            setattr(m, k, np.concatenate([getattr(p, k) for p in parts]))
+        return m
+
+
+def measure_spec(ny, start=0, length=0, f0=None, harmonics=0, rows=None):
+    """((start, length, f_num, f_den, harmonics, row mask), measured rows) -- acme_batch_set_measurement's arguments -- from
+    ``ModelRunner.set_measurement``'s: ``f0`` a Fraction of fs or
+    (num, den); ``rows`` the output rows to measure (None: all)."""
+    from fractions import Fraction
+    if f0 is None:
+        if harmonics:
+            raise ValueError("harmonics need a fundamental f0")
+        num, den = 0, 1
+    elif isinstance(f0, tuple):
+        num, den = (int(v) for v in f0)
+    else:
+        f = Fraction(f0)
+        num, den = f.numerator, f.denominator
+    mask = 0
+    rows = list(range(min(ny, 64))) if rows is None else sorted(set(int(r) for r in rows))
+    for r in rows:
+        if r < 0 or r >= 64:          # (the mask has 64 bits; the library refuses rows beyond the model's outputs)
+            raise DimensionMismatch(f"output row {r}: rows 0 ... 63 can be measured")
+        mask |= 1 << r
+    return (int(start), int(length), num, den, int(harmonics), mask if rows else 0), rows
 
 
 def _ip(a):
@@ -265,6 +324,7 @@ class ModelRunner:
         self.h = h
         self._warned = 0
         self._os = (1, 1, 1)            # oversampling: factor, interpolation taps, decimation taps
+        self._meas = None               # measurement: (harmonics, measured rows) while armed
         self._progress_cb = None
         if showprogress:
             fn = showprogress if callable(showprogress) else _print_progress
@@ -320,6 +380,62 @@ class ModelRunner:
             return 0
         d = ((lu - 1) + (ld - 1)) / (2 * k)
         return int(d) if d == int(d) else d
+
+    # ---- output measurements ------------------------------------------------------------------
+    def set_measurement(self, start=0, length=0, f0=None, harmonics=0, rows=None):
+        """Arm an output measurement (``acme_batch_set_measurement``): from now on every run feeds per instance and output
+        row (``rows``: which, None = all) the mean, RMS, min, max and the complex amplitudes of ``harmonics`` harmonics of
+        the fundamental ``f0`` -- a ``Fraction`` of fs or ``(num, den)`` -- over the samples ``start <= n < start + length``
+        counted from now (``length=0``: all from ``start`` on).  ``measure`` then runs without storing y at all."""
+        spec, rows = measure_spec(self.model.ny, start, length, f0, harmonics, rows)
+        self.lib.check(self.lib.L.acme_batch_set_measurement(self.h, *spec))
+        self._meas = (int(harmonics), rows)
+        return self
+
+    def clear_measurement(self):
+        """switch the measurement off (``acme_batch_clear_measurement``)"""
+        self.lib.check(self.lib.L.acme_batch_clear_measurement(self.h))
+        self._meas = None
+        return self
+
+    def reset_measurement(self):
+        """zero the accumulators and restart the window's clock (``acme_batch_reset_measurement``)"""
+        self.lib.check(self.lib.L.acme_batch_reset_measurement(self.h))
+        return self
+
+    def measurement(self):
+        """the armed measurement's results so far (``acme_batch_get_measurement``): a ``Measurement``"""
+        if self._meas is None:
+            raise AcmeError("no measurement is armed")
+        H, rows = self._meas
+        out = np.empty((self.n, len(rows), 4 + 2 * H))
+        count = C.c_longlong(0)
+        self.lib.check(self.lib.L.acme_batch_get_measurement(self.h, _dp(out), C.byref(count)))
+        return Measurement(out, count.value, rows)
+
+    def measure(self, u, check=True, time_major=False):
+        """``run`` without outputs: advance the instances over ``u`` (shapes as ``run``) and only feed the armed
+        measurement (y = NULL: nothing of y is stored or copied).  Returns ``self``; ``measurement()`` reads the results."""
+        m = self.model
+        u = np.asarray(u, dtype=np.float64)
+        if not time_major:
+            if u.ndim == 2 and self.n == 1:
+                u = u[None]
+            if u.ndim != 3 or u.shape[0] != self.n or u.shape[1] != m.nu:
+                raise DimensionMismatch(f"input must have shape ({self.n}, {m.nu}, T)")
+            u = np.transpose(u, (0, 2, 1))
+        if u.ndim != 3 or u.shape[0] != self.n or u.shape[2] != m.nu:
+            raise DimensionMismatch(f"input must have shape ({self.n}, T, {m.nu})")
+        ub = np.ascontiguousarray(u)
+        self.lib.check(self.lib.L.acme_batch_run(self.h, ub.ctypes.data, None, ub.shape[1], ACME_MEM_HOST, None))
+        self._hold(ub)
+        if check:
+            self.check()
+        return self
+
+    def measure_const(self, u_var, u_const, const_rows, check=True):
+        """``run_const`` without outputs (y = NULL): only the armed measurement is fed.  Returns ``self``."""
+        return self.run_const(u_var, u_const, const_rows, y=False, check=check)
 
     def set_balance(self, mode=-1):
         """Placement of the waves by their measured cost (``acme_batch_set_balance``): -1 the library decides
@@ -473,6 +589,12 @@ class ModelRunner:
         if u_const.shape != (self.n, m.nu):
             raise DimensionMismatch(f"u_const must have shape ({self.n}, {m.nu})")
         T = u_var.shape[1]
+        if y is False:                  # (measure_const: no outputs)
+            self.lib.check(self.lib.L.acme_batch_run_const(self.h, u_var.ctypes.data, u_const.ctypes.data, mask, None, T, ACME_MEM_HOST, None))
+            self._hold(u_var, u_const)
+            if check:
+                self.check()
+            return self
         if y is None:
             y = np.empty((self.n, T, m.ny), dtype=np.float64)
         elif not (isinstance(y, np.ndarray) and y.dtype == np.float64 and y.flags.c_contiguous and y.shape == (self.n, T, m.ny)):
@@ -486,8 +608,18 @@ class ModelRunner:
     def run_async(self, u, y):
         """``acme_batch_run_async`` on host buffers in the ABI's layout: ``u`` (N, T, nu) and ``y``
         (N, T, ny), C-contiguous float64 (slices of larger arrays along the first axis are fine).
-        Returns at once; ``wait()`` joins the run.  The caller keeps ``u`` / ``y`` alive until then."""
+        Returns at once; ``wait()`` joins the run.  The caller keeps ``u`` / ``y`` alive until then.  ``y=None`` while a
+        measurement is armed: the run only feeds the measurement."""
         m = self.model
+        if y is None and self._meas is not None:
+            if not (isinstance(u, np.ndarray) and u.dtype == np.float64 and u.flags.c_contiguous):
+                raise TypeError("u must be a C-contiguous float64 array")
+            if u.ndim != 3 or u.shape[0] != self.n or u.shape[2] != m.nu:
+                raise DimensionMismatch(f"u must have shape ({self.n}, T, {m.nu})")
+            self._inflight = (u,)
+            self._hold(u)
+            self.lib.check(self.lib.L.acme_batch_run_async(self.h, u.ctypes.data, None, u.shape[1], ACME_MEM_HOST, None))
+            return
         for a, cols, what in ((u, m.nu, "u"), (y, m.ny, "y")):
             if not (isinstance(a, np.ndarray) and a.dtype == np.float64 and a.flags.c_contiguous):
                 raise TypeError(f"{what} must be a C-contiguous float64 array")
@@ -672,10 +804,47 @@ class MultiDeviceRunner:
                 r.set_oversampling(factor, up, down, held_rows)
         return self
 
+    def set_measurement(self, start=0, length=0, f0=None, harmonics=0, rows=None):
+        """``ModelRunner.set_measurement`` on every device's batch"""
+        for r in self.runners:
+            if r is not None:
+                r.set_measurement(start, length, f0, harmonics, rows)
+        return self
+
+    def reset_measurement(self):
+        for r in self.runners:
+            if r is not None:
+                r.reset_measurement()
+        return self
+
+    def measurement(self):
+        """the shards' ``Measurement`` results, concatenated along the instances"""
+        return Measurement.concatenate([r.measurement() for r in self.runners if r is not None])
+
+    def measure(self, u, check=True):
+        """``run`` with y = NULL on every device (``u``: (N, T, nu), the ABI's layout); only the measurements are fed."""
+        return self.run(u, y=False, check=check)
+
     def run(self, u, y=None, check=True):
         """``u``: (N, T, nu) C-contiguous float64 (the ABI's layout); returns / fills ``y`` (N, T, ny)."""
         m = self.model
         u = np.ascontiguousarray(u, dtype=np.float64)
+        if y is False:                  # (measure: no outputs)
+            if u.ndim != 3 or u.shape[0] != self.n or u.shape[2] != m.nu:
+                raise DimensionMismatch(f"input must have shape ({self.n}, T, {m.nu})")
+            started, err = [], None
+            for r, (lo, hi) in zip(self.runners, self.ranges):
+                if r is not None:
+                    r.run_async(u[lo:hi], None)
+                    started.append(r)
+            for r in started:
+                try:
+                    r.wait(check=check)
+                except AcmeError as e:
+                    err = err or e
+            if err is not None:
+                raise err
+            return self
         if u.ndim != 3 or u.shape[0] != self.n or u.shape[2] != m.nu:
             raise DimensionMismatch(f"input must have shape ({self.n}, T, {m.nu})")
         if y is None:

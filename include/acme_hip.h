@@ -160,7 +160,9 @@ int acme_batch_set_matrices(acme_batch *b, long long first, long long count,
  *   callback installed, for memory that cannot be page-locked, for batches of more blocks than the chip holds at
  *   once, nor for the lane-per-instance and generic kernels (time slices).  The call returns when y is complete;
  * mem = ACME_MEM_DEVICE: u/y are device pointers on the batch's device and `stream` is the
- * hipStream_t to launch on (NULL = default stream); the call is then asynchronous. */
+ * hipStream_t to launch on (NULL = default stream); the call is then asynchronous.
+ * y = NULL is accepted (here, by acme_batch_run_const and by acme_batch_run_async) only while a measurement is armed
+ * (acme_batch_set_measurement, below). */
 int acme_batch_run(acme_batch *b, const double *u, double *y, long long T, int mem,
                    void *stream);
 /* run! with CONSTANT input rows (src/ACME.jl:672-674 copies column n of u into ucur sample by sample: a row that never
@@ -227,6 +229,46 @@ int acme_oversampling_design(int factor, double *taps, int capacity);
  * its arguments (ACME_ERR_INVALID) and resets the histories. */
 int acme_batch_set_oversampling(acme_batch *b, int factor, const double *h_up, int n_up, const double *h_down, int n_down,
                                 unsigned long long held_rows);
+
+/* Output measurements.  What a sweep usually wants back is a few numbers per cell -- DC offset, RMS, peak, the gain at the
+ * fundamental, the harmonic distortion (SPICE's .four / .meas) --, not all of y.  While a measurement is armed, every run
+ * entry point (acme_batch_run, _run_const, _run_async; host and device memory; oversampled batches: the base-rate y, after
+ * decimation) feeds the library's accumulators on the device, and y may be NULL: nothing of it is then written, staged or
+ * copied back (the device needs one time slice of output scratch, not [N][T][ny]).
+ *   window      samples are counted from arming (acme_batch_set_measurement / _reset_measurement) across every later run;
+ *               sample n counts when start <= n < start + length (length 0: every sample from start on); m = n - start
+ *   per instance and measured row, each accumulator ONE chain in sample order:
+ *               sum += y;  sq = fma(y, y, sq);  min;  max;
+ *               C_h = fma(y, cos th, C_h),  S_h = fma(y, sin th, S_h)  for h = 1 ... H,
+ *               th = 2 pi ((h f_num m) mod f_den) / f_den  (the phase reduced exactly in 64-bit integers)
+ *   results     acme_batch_get_measurement writes out[N][nrows][4 + 2H]: mean = sum / count, RMS = sqrt(sq / count), min,
+ *               max, then Re and Im of A_h = (2 / count) (C_h - j S_h) for h = 1 ... H -- the complex amplitude of the h-th
+ *               harmonic (y = |A_h| cos(h w n + arg A_h) gives A_h over whole periods); rows ascending; count = samples
+ *               measured (0: NaN means).
+ * Results do not depend on time slices, host or device memory, the entry point, split calls or whether y is stored (bit for
+ * bit).  An instance past its first_nonfinite sample (NaN outputs) measures NaN; the others are unaffected.  While a
+ * measurement is armed, host-buffer runs take the staged slice pipeline, never the streamed path of
+ * acme_batch_set_host_retention.  acme_batch_set_matrices, _set_state, _reset_report and _set_oversampling leave the
+ * accumulators and the window's position alone.  Not together with acme_batch_set_isolation (ACME_ERR_UNSUPPORTED either way
+ * round).  Nothing armed: no launch, allocation or synchronisation of any run changes. */
+#define ACME_MAX_HARMONICS 32
+/* arm a measurement (zeroed accumulators, the window's clock at 0):
+ *   start, length   first measured sample, counted in base-rate samples from arming; number of measured samples (0 = every
+ *                   sample from start on)
+ *   f_num, f_den    fundamental = f_num / f_den x the base sample rate (0 < f_den < 2^31)
+ *   harmonics       H = 0 ... ACME_MAX_HARMONICS harmonics of the fundamental
+ *   rows            output rows measured, bit r = row r; 0 = all rows (ny <= 64)
+ * Validates its arguments (ACME_ERR_INVALID).  Completes the batch's outstanding work first.  (The window's parameters go
+ * as plain arguments, not as a struct: a binding needs no mirror of the layout.) */
+int acme_batch_set_measurement(acme_batch *b, long long start, long long length, long long f_num, long long f_den,
+                               int harmonics, unsigned long long rows);
+/* switch the measurement off (y = NULL is refused again) */
+int acme_batch_clear_measurement(acme_batch *b);
+/* zero the accumulators and restart the window's clock (the armed parameters stay) */
+int acme_batch_reset_measurement(acme_batch *b);
+/* out: [N][nrows][4 + 2H] doubles as above (may be NULL); *count: samples measured (may be NULL).  Joins a pending
+ * acme_batch_run_async and synchronises the device. */
+int acme_batch_get_measurement(acme_batch *b, double *out, long long *count);
 
 /* acme_batch_run without blocking the caller: the same run on a worker thread of the library (a
  * host-buffer run drives its time-slice pipeline from there).  ONE host thread can thereby keep one

@@ -34,7 +34,8 @@ import ProgressMeter
 import ACME: run!, solve, hasconverged, needediterations, set_resabstol!,
              get_extrapolation_origin, set_extrapolation_origin, get_extrapolation_jacobian
 
-export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host_buffers!, release_host_buffers!, set_isolation!, set_balance!
+export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host_buffers!, release_host_buffers!, set_isolation!, set_balance!,
+       MeasureSpec, Measurement, set_measurement!, clear_measurement!, reset_measurement!, measurement, measure!
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
 
@@ -45,6 +46,7 @@ const ACME_MAX_ELEM_PAR = 16
 const ACME_SOLVER_SIMPLE, ACME_SOLVER_HOMOTOPY, ACME_SOLVER_CACHING_HOMOTOPY = Cint(0), Cint(1), Cint(2)
 const ACME_MEM_HOST, ACME_MEM_DEVICE = Cint(0), Cint(1)
 const ACME_MAX_OVERSAMPLING = 16
+const ACME_MAX_HARMONICS = 32
 const KIND_NQ = Dict(1 => 2, 2 => 4, 3 => 5, 4 => 3, 5 => 2, 6 => 4)
 const KIND_NN = Dict(1 => 1, 2 => 2, 3 => 2, 4 => 1, 5 => 1, 6 => 1)
 
@@ -205,6 +207,7 @@ mutable struct BatchRunner
     warned::Int
     progress::Base.RefValue{Any}      # the ProgressMeter.Progress of the run in flight (showprogress = true)
     showprogress::Bool
+    meas::Any                         # the armed MeasureSpec (nothing: none)
 end
 
 # @showprogress of run!(runner, y, u) (src/ACME.jl:587-604,653): the library reports after every time slice of a
@@ -223,7 +226,7 @@ function BatchRunner(model::DiscreteModel, n::Integer; device::Integer=-1,
     b = Ref{Ptr{Cvoid}}()
     check(ccall((:acme_batch_create, lib), Cint, (Ptr{Cvoid}, Clonglong, Ref{AcmeOptions}, Ref{Ptr{Cvoid}}),
                 mh.h, n, opts, b))
-    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress)
+    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress, nothing)
     finalizer(r -> ccall((:acme_batch_destroy, lib), Cvoid, (Ptr{Cvoid},), r.h), r)
     if showprogress
         cb = @cfunction(progress_trampoline, Cvoid, (Ptr{Cvoid}, Clonglong, Clonglong))
@@ -407,6 +410,107 @@ function run!(r::BatchRunner, y::Array{Float64,3}, u_var::Array{Float64,3}, u_co
                 (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Culonglong, Ptr{Cdouble}, Clonglong, Cint, Ptr{Cvoid}),
                 r.h, u_var, u_const, mask, y, size(u_var, 2), ACME_MEM_HOST, C_NULL))
     return checkreports!(r)
+end
+
+# ---- output measurements ---------------------------------------------------------------------------------------
+"""
+    MeasureSpec(; start=0, length=0, f0=0//1, harmonics=0, rows=())
+
+The window and quantities of an output measurement -- the arguments of `acme_batch_set_measurement`: samples
+`start <= n < start + length` counted from arming (`length = 0`: all from `start` on), the fundamental `f0` as a
+`Rational` of the sample rate, `harmonics` (0 ... 32) of it, the output `rows` measured (1-based; empty: all).
+"""
+struct MeasureSpec
+    start::Int64
+    length::Int64
+    f_num::Int64
+    f_den::Int64
+    harmonics::Int32
+    rows::UInt64
+end
+function MeasureSpec(; start::Integer=0, length::Integer=0, f0::Rational=0//1, harmonics::Integer=0, rows=())
+    mask = UInt64(0)
+    for k in rows
+        1 <= k <= 64 || throw(DimensionMismatch("output row $k: rows 1 ... 64 can be measured"))
+        mask |= UInt64(1) << (k - 1)
+    end
+    return MeasureSpec(start, length, numerator(f0), denominator(f0), harmonics, mask)
+end
+
+"""
+What `measurement(runner)` returns, per instance and measured row (`rows`, 1-based, ascending): `mean`, `rms`, `min`,
+`max` (nrows x N) and `harmonics` (H x nrows x N), the complex amplitudes A_h = (2 / count) sum_m y[m] exp(-j h w m);
+`count` samples were measured.  `peak(m)`, `thd(m)`.
+"""
+struct Measurement
+    count::Int
+    rows::Vector{Int}
+    mean::Matrix{Float64}
+    rms::Matrix{Float64}
+    min::Matrix{Float64}
+    max::Matrix{Float64}
+    harmonics::Array{ComplexF64,3}
+end
+peak(m::Measurement) = max.(abs.(m.min), abs.(m.max))
+"total harmonic distortion sqrt(sum_{h >= 2} |A_h|^2) / |A_1| (nrows x N)"
+thd(m::Measurement) = dropdims(sqrt.(sum(abs2, m.harmonics[2:end, :, :]; dims=1)) ./ abs.(m.harmonics[1:1, :, :]); dims=1)
+
+"""
+    set_measurement!(runner, spec::MeasureSpec)
+    set_measurement!(runner; start=0, length=0, f0=0//1, harmonics=0, rows=())
+
+Arm an output measurement (`acme_batch_set_measurement`): from now on every `run!` / `measure!` feeds per instance and
+measured output row the mean, RMS, min, max and the complex amplitudes of the fundamental's harmonics over the window
+-- on the GPU, in place of the outputs a sweep would otherwise have to keep.  `measure!` then runs without `y`.
+"""
+function set_measurement!(r::BatchRunner, spec::MeasureSpec)
+    check(ccall((:acme_batch_set_measurement, lib), Cint,
+                (Ptr{Cvoid}, Clonglong, Clonglong, Clonglong, Clonglong, Cint, Culonglong),
+                r.h, spec.start, spec.length, spec.f_num, spec.f_den, spec.harmonics, spec.rows))
+    r.meas = spec
+    return r
+end
+set_measurement!(r::BatchRunner; kwargs...) = set_measurement!(r, MeasureSpec(; kwargs...))
+
+"switch the measurement off (`acme_batch_clear_measurement`)"
+function clear_measurement!(r::BatchRunner)
+    check(ccall((:acme_batch_clear_measurement, lib), Cint, (Ptr{Cvoid},), r.h))
+    r.meas = nothing
+    return r
+end
+
+"zero the accumulators and restart the window's clock (`acme_batch_reset_measurement`)"
+reset_measurement!(r::BatchRunner) = (check(ccall((:acme_batch_reset_measurement, lib), Cint, (Ptr{Cvoid},), r.h)); r)
+
+"the armed measurement's results so far (`acme_batch_get_measurement`)"
+function measurement(r::BatchRunner)
+    spec = r.meas
+    spec === nothing && error("no measurement is armed")
+    ny = ACME.ny(r.model)
+    rows = spec.rows == 0 ? collect(1:min(ny, 64)) : [k for k in 1:64 if (spec.rows >> (k - 1)) & 1 == 1]
+    H = Int(spec.harmonics)
+    out = Array{Float64,3}(undef, 4 + 2H, length(rows), r.n)        # the ABI's [N][nrows][4 + 2H]
+    count = Ref{Clonglong}(0)
+    check(ccall((:acme_batch_get_measurement, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ref{Clonglong}), r.h, out, count))
+    return Measurement(count[], rows, out[1, :, :], out[2, :, :], out[3, :, :], out[4, :, :],
+                       complex.(out[5:2:end, :, :], out[6:2:end, :, :]))
+end
+
+"""
+    measure!(runner, u::Array{Float64,3})
+
+`run!` without outputs: advance the instances over `u` (`nu × T × N`) and only feed the armed measurement -- y = NULL,
+nothing of the outputs is written, staged or copied back.
+"""
+function measure!(r::BatchRunner, u::Array{Float64,3})
+    r.meas === nothing && error("measure! needs an armed measurement (set_measurement!)")
+    size(u, 1) == ACME.nu(r.model) || throw(DimensionMismatch("input matrix has $(size(u,1)) rows, but model has $(ACME.nu(r.model)) inputs"))
+    size(u, 3) == r.n || throw(DimensionMismatch("u needs one nu × T slice per instance ($(r.n))"))
+    GC.@preserve r check(ccall((:acme_batch_run, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Clonglong, Cint, Ptr{Cvoid}),
+                r.h, u, C_NULL, size(u, 2), ACME_MEM_HOST, C_NULL))
+    checkreports!(r)
+    return r
 end
 
 # ---- MultiBatchRunner: N instances over the GPUs of one node, one Julia process -----------------------
