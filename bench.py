@@ -9,8 +9,10 @@ point of a drive x tone x level grid, 1 kHz unit sine, one "step" = 1 s of audio
 model block is broadcast once over RCCL before the timed region, and the only collective
 inside it is the all-reduce of the per-rank solver counters.
 
-Prints ONE JSON line on rank 0 (contract in the task description) with two extra objects:
+Prints ONE JSON line on rank 0 (contract in the task description) with an extra object:
   roofline     -- algorithmic HBM bytes per launch / kernel time measured with HIP events
+A plain run does only what that line's headline figure needs: set-up, warm-up, the timed steps, --dump-outputs and
+the line.  Everything else the benchmark measures runs with --full only (extra_legs), among it
   cpu_baseline -- the CPU oracle (a C restatement of the reference algorithm, NOT the Julia
                   reference, which cannot run here) timed on the host cores of this box
 """
@@ -702,11 +704,34 @@ def host_buffer_leg(runner, u, N, T, model):
     return out
 
 
-def main():
+def extra_legs(args, world):
+    """The legs a run adds after its timed steps, beyond the headline figure -- none without --full:
+      host_path       config.host_buffers: run! through host buffers on the timed batch (one rank only)
+      other_workloads config.other_workloads: BASELINE configs 2, 4, 5 and the clipper chains (headline workload, one rank)
+      mid_size        config.mid_size: the mid-size kernel at 24 ... 64 unknowns (headline workload, one rank)
+      literal_grid    config.literal_grid: the literal config-3 grid with its singular column (headline workload, one rank)
+      cpu_baseline    cpu_baseline: the CPU oracle on a sample of the same workload, and the Julia probe (one rank)
+      gather          config.gather_ms: the collection of the sharded outputs on rank 0 (more than one rank)
+    The --no-* options take single legs out of a --full run.  --saturation and an explicit --gather are asked for on
+    their own, with or without --full."""
+    if not args.full:
+        return set()
+    legs = {"gather"} if world > 1 else set()
+    if world == 1:
+        if not args.no_host_path:
+            legs.add("host_path")
+        if not args.no_cpu_baseline:
+            legs.add("cpu_baseline")
+        if args.workload == "superover_grid" and not args.no_other_workloads:
+            legs |= {"other_workloads", "mid_size"} | (set() if args.no_literal_grid else {"literal_grid"})
+    return legs
+
+
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     # (defaults = the driver's command: the first steps of a fresh batch learn their solution caches and have no measured
-    # wave costs to place by -- a step is 0.27 s, the whole default run about a minute and a half)
+    # wave costs to place by -- a step is 0.27 s; a plain run adds seconds of set-up to its steps, --full a minute and a half)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="superover_grid",
@@ -717,8 +742,13 @@ def main():
                          "clipper_chain_20 / _34 = beyond BASELINE, one 20- / 34-unknown sub-problem on the mid-size kernel (rows in registers / "
                          "matrix in LDS, one instance per wave), 0.1 s per step")
     ap.add_argument("--instances", type=int, default=None, help="instances per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything beyond the headline figure (bench.extra_legs): the "
+                         "host-buffer leg, the other workloads, the mid-size sizes, the literal grid, the CPU baseline, and the "
+                         "output collection at N > 1; off by default")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip the short steady-state legs of BASELINE configs 2, 4, 5 (config.other_workloads) that follow the headline")
+                    help="with --full: skip the short steady-state legs of BASELINE configs 2, 4, 5 (config.other_workloads), "
+                         "the mid-size sizes (config.mid_size) and the literal grid that follow the headline")
     ap.add_argument("--samples", type=int, default=None, help="samples per step (default: 1 s of signal)")
     ap.add_argument("--solver", default=None, choices=["caching", "homotopy", "simple"],
                     help="caching = HomotopySolver{CachingSolver{SimpleSolver}}, the reference's default stack "
@@ -726,21 +756,27 @@ def main():
     ap.add_argument("--gather", default=None, choices=["none", "rank0", "allgather"],
                     help="collection of the sharded outputs after the timed steps, timed separately (gather_ms): "
                          "rank0 = every rank sends its y to rank 0 (grouped send/recv), allgather = RCCL all-gather; "
-                         "default: rank0 when N > 1, none at N = 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                         "default: rank0 with --full when N > 1, else none")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (cpu_baseline)")
     ap.add_argument("--no-host-path", action="store_true",
-                    help="skip the host-buffer leg (config.value_host_buffers: run! through acme_batch_run(ACME_MEM_HOST), "
-                         "what the Julia binding calls)")
+                    help="with --full: skip the host-buffer leg (config.value_host_buffers: run! through "
+                         "acme_batch_run(ACME_MEM_HOST), what the Julia binding calls)")
     ap.add_argument("--cpu-samples", type=int, default=None)
     ap.add_argument("--saturation", action="store_true",
                     help="also measure every workload at 1 / 2 / 4 / 8 x its BASELINE per-GPU instance count (config.saturation; "
                          "several minutes; all 16 384 instances of config 5 on one GPU among them)")
     ap.add_argument("--no-literal-grid", action="store_true",
-                    help="skip the leg on the LITERAL config-3 grid, drive = linspace(0, 1, 32) with its singular column (config.literal_grid)")
+                    help="with --full: skip the leg on the LITERAL config-3 grid, drive = linspace(0, 1, 32) with its singular "
+                         "column (config.literal_grid)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the output y [instances, samples, ny] of the last timed step as DIR/y.npy "
                          "(DIR/y_rank<r>.npy per rank when N > 1), float64: all of it, or a fixed seeded sample of instances "
                          "(bench.dump_sample) that keeps the files below 64 MB together")
+    return ap
+
+
+def main():
+    ap = arg_parser()
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
@@ -766,6 +802,7 @@ def main():
     # ACME_BENCH_FORCE_DIST=1: take the multi-rank code path (RCCL init, broadcast, all-reduce,
     # barriers) even at world size 1 -- what the single-GPU box can check of it (tests)
     use_dist = world > 1 or os.environ.get("ACME_BENCH_FORCE_DIST") == "1"
+    legs = extra_legs(args, world)       # (empty in a plain run)
     if use_dist:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         os.environ.setdefault("MASTER_PORT", "29533")
@@ -862,10 +899,10 @@ def main():
     # Collection of the sharded outputs (SURVEY 8e / north star: "gather of outputs over xGMI"): the
     # last step's y of every rank, timed on its own between barriers.  It is not part of `value`
     # (instances never interact: no collective sits on the data path); `value_incl_gather` charges
-    # one such collection to every step.
-    gather_mode = args.gather or ("rank0" if use_dist and world > 1 else "none")
+    # one such collection to every step: with --full, or when --gather asks for it.
+    gather_mode = args.gather or ("rank0" if use_dist and "gather" in legs else "none")
     if os.environ.get("ACME_BENCH_FORCE_DIST") == "1" and args.gather is None:
-        gather_mode = "rank0"          # single-rank rehearsal of the collective path (tests)
+        gather_mode = "rank0"          # single-rank rehearsal of the collective path (tests), with or without --full
     gather_ms = gathered_shape = None
     if gather_mode != "none" and use_dist:
         from acme_jl_amd.dist import collect_outputs
@@ -888,13 +925,13 @@ def main():
     # in time slices whose copies overlap the kernel.  First call: page-locks the arrays; steady: the same arrays again
     # (a caller reusing its arrays); pageable: ACME_HOST_REGISTER=0.  Never `value`.
     host = None
-    if world == 1 and not args.no_host_path:
+    if "host_path" in legs:
         host = host_buffer_leg(runner, u, n_per_gpu, T, model)
     # BASELINE configs 2, 4 and 5 next to the headline (config 3): one short steady-state measurement each, reported
-    # under config.other_workloads -- every BASELINE number in the driver's own record -- and, beyond BASELINE, one
+    # under config.other_workloads -- every BASELINE number in the --full record -- and, beyond BASELINE, one
     # 20-unknown sub-problem on the mid-size kernel (config: null).  Never `value`.
     others = None
-    if world == 1 and args.workload == "superover_grid" and not args.no_other_workloads:
+    if "other_workloads" in legs:
         others = []
         for wl in ("diodeclipper_sweep", "superover_montecarlo", "birdie_grid", "clipper_chain_20", "clipper_chain_34"):
             try:
@@ -902,10 +939,10 @@ def main():
             except Exception as e:      # (the headline line must come out whatever happens here)
                 others.append({"workload": wl, "error": repr(e)})
     mid = None
-    if world == 1 and args.workload == "superover_grid" and not args.no_other_workloads:
+    if "mid_size" in legs:
         mid = mid_size_leg(local_rank, dev)
     literal = saturation = None
-    if world == 1 and args.workload == "superover_grid" and not args.no_other_workloads and not args.no_literal_grid:
+    if "literal_grid" in legs:
         try:
             literal = literal_grid_leg(local_rank, dev)
         except Exception as e:
@@ -1020,7 +1057,7 @@ def main():
             assert len(set(checksums)) == world, f"ranks computed identical shards: {checksums}"
         if out["roofline"]["fp64_reference_equivalent_tflops"] is not None:
             out["roofline"]["fp64_reference_equivalent_frac"] = out["roofline"]["fp64_reference_equivalent_tflops"] / FP64_PEAK_TFLOPS
-        if world == 1 and not args.no_cpu_baseline:
+        if "cpu_baseline" in legs:
             T_cpu = args.cpu_samples or min(T, FS)
             out["cpu_baseline"] = cpu_baseline(fixture, model, pots, amp, T_cpu, fs=fs)
             # the real reference, if this box has a Julia (null: `julia` not on PATH)

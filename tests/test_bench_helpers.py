@@ -121,6 +121,24 @@ def test_native_cpu_leg_times_the_native_build():
         os.remove(native)
 
 
+def test_plain_run_measures_nothing_beyond_its_headline():
+    """A plain run (no --full) adds no leg after its timed steps; --full adds what the default run measured before, the
+    --no-* options take single legs out of it, and the one-rank-only legs never run on more ranks."""
+    def legs(*argv, world=1):
+        return bench.extra_legs(bench.arg_parser().parse_args(list(argv)), world)
+    assert not bench.arg_parser().parse_args([]).full
+    for argv in ([], ["--gpus", "1", "--steps", "3", "--warmup", "2"], ["--workload", "birdie_grid"], ["--dump-outputs", "d"]):
+        assert legs(*argv) == set() and legs(*argv, world=8) == set()
+    everything = {"host_path", "other_workloads", "mid_size", "literal_grid", "cpu_baseline"}
+    assert legs("--full") == everything
+    assert legs("--full", world=8) == {"gather"}
+    assert legs("--full", "--workload", "birdie_grid") == {"host_path", "cpu_baseline"}
+    assert legs("--full", "--no-cpu-baseline") == everything - {"cpu_baseline"}
+    assert legs("--full", "--no-host-path") == everything - {"host_path"}
+    assert legs("--full", "--no-literal-grid") == everything - {"literal_grid"}
+    assert legs("--full", "--no-other-workloads") == {"host_path", "cpu_baseline"}
+
+
 def test_dump_outputs_writes_a_fixed_sample_within_the_budget(tmp_path):
     """--dump-outputs: the whole output when it fits, else the same seeded instances (and, for one over-long instance, the
     same seeded samples) on every run, within the byte budget; the file holds exactly those entries of y, in float64."""

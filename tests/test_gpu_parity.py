@@ -488,6 +488,30 @@ def test_bench_multirank_path_over_rccl(hip_lib):
     assert rec["config"]["gathered_shape"] == [256, 2000, 1]
 
 
+def test_plain_bench_run_is_the_headline_alone(hip_lib, tmp_path):
+    """bench.py without --full on one GPU: the result line with its headline figures and the dumped outputs, and none of
+    the legs that --full adds after the timed steps."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--instances", "256", "--samples", "2000", "--dump-outputs", str(tmp_path)]
+    out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=280)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rec = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    assert rec["metric"] == "circuit-instance*samples/sec (superover, 44.1 kHz)" and rec["unit"] == "circuit-instance*samples/sec"
+    assert rec["higher_is_better"] is True and rec["dtype"] == "f64" and rec["steps"] == 2 and rec["warmup"] == 1
+    assert rec["value"] > 1e6 and abs(rec["value"] * rec["ms_per_step"] * 1e-3 - 256 * 2000) < 1e-6 * 256 * 2000
+    cfg = rec["config"]
+    assert cfg["n_warn"] == 0 and cfg["n_nonfinite_instances"] == 0 and cfg["y_abs_sum_rank0"] > 0
+    assert "cpu_baseline" not in rec and cfg["gather"] == "none" and cfg["gather_ms"] is None
+    assert all(cfg[k] is None for k in ("host_buffers", "other_workloads", "mid_size", "literal_grid", "saturation"))
+    y = np.load(tmp_path / "y.npy")
+    assert y.shape == (256, 2000, 1) and cfg["dump_outputs"]["shape"] == [256, 2000, 1]
+    assert abs(float(np.abs(y).sum()) - cfg["y_abs_sum_rank0"]) <= 1e-9 * cfg["y_abs_sum_rank0"]
+
+
 # Ranks of the one-device rehearsal: with the test process itself, at most six processes may have the shared GPU open
 # at once.
 REHEARSAL_RANKS = 4
