@@ -4,7 +4,9 @@ import numpy as np
 
 
 def twiddles(f_num, f_den, H, m):
-    """cos / sin [H, len(m)] of 2 pi ((h f_num m) mod f_den) / f_den, the phase reduced exactly in integers"""
+    """cos / sin [H, len(m)] of 2 pi ((h f_num m) mod f_den) / f_den, the phase reduced exactly in integers -- int64 and
+    np.cos of the rounded angle, the library's own steps: it cannot disagree with meas_twiddle about the phase.  The
+    independent form (unbounded integers, mpmath) is exact_ref.exact_twiddles."""
     h = np.arange(1, H + 1, dtype=np.int64)[:, None]
     k = (h * (f_num % f_den) % f_den) * (np.asarray(m, dtype=np.int64)[None] % f_den) % f_den
     k = np.where(2 * k > f_den, k - f_den, k)
