@@ -3,6 +3,7 @@
 // GPU-less unit tests (tests/emu) share every line of host logic.  Included, not compiled alone.
 #include "acme_resample.h"
 #include "acme_measure.h"
+#include "acme_source.h"
 // ------------------------------------------------------------------------------------------
 // handles
 // ------------------------------------------------------------------------------------------
@@ -148,6 +149,17 @@ struct acme_batch {
         double *d_ys = nullptr;                  // y = NULL: one slice of base-rate outputs, [N][TS][ny]
         size_t cap_ys = 0;
     } meas;
+    // Input rows generated on the device (acme_batch_set_source_*, acme_source.h): the rows' descriptions and per-instance
+    // parameters in device memory, the source clock
+    struct Sources {
+        int armed = 0;                           // rows with a source (0: none of the members below is used)
+        unsigned long long mask = 0, cmask = 0;  // the rows with a source; those of kind CONST (held on an oversampled batch)
+        long long clock = 0;                     // base-rate samples since the first source was armed
+        SrcRow row[64] = {};                     // as the device sees them (the pointers are device pointers)
+        SrcRow *d_rows = nullptr;                // [64]
+        double *d_ys = nullptr;                  // device arrays, y stored, no oversampling: one slice of packed outputs
+        size_t cap_ys = 0;
+    } src;
     // acme_batch_run_async: the run in flight on a worker thread of the library, its status and message
     std::thread worker;
     int worker_rc = ACME_OK;
@@ -159,6 +171,21 @@ struct acme_batch {
 // The run's own status is kept for acme_batch_wait.
 static void join_worker(acme_batch *b) {
     if (b && b->worker.joinable()) b->worker.join();
+}
+
+// free the per-instance parameters of input row `row`'s source (row < 0: of every row) and mark the row as the caller's
+static void src_release(acme_batch *b, int row) {
+    acme_batch::Sources &S = b->src;
+    for (int r = row < 0 ? 0 : row; r < (row < 0 ? 64 : row + 1); ++r) {
+        SrcRow &R = S.row[r];
+        if (R.kind == SRC_NONE) continue;
+        (void)be::dfree(const_cast<double *>(R.amp)); (void)be::dfree(const_cast<double *>(R.off)); (void)be::dfree(const_cast<double *>(R.w));
+        (void)be::dfree(const_cast<long long *>(R.fnum)); (void)be::dfree(const_cast<long long *>(R.phase));
+        R = SrcRow{};
+        S.mask &= ~(1ull << r);
+        S.cmask &= ~(1ull << r);
+        --S.armed;
+    }
 }
 
 static void release_reg(acme_batch::HostReg &r) {
@@ -718,6 +745,8 @@ void acme_batch_destroy(acme_batch *b) {
     (void)be::dfree(b->os.d_taps); (void)be::dfree(b->os.d_hist_u); (void)be::dfree(b->os.d_hist_y);
     (void)be::dfree(b->os.d_ou); (void)be::dfree(b->os.d_oy); (void)be::dfree(b->os.d_base);
     (void)be::dfree(b->meas.d_acc); (void)be::dfree(b->meas.d_tw); (void)be::dfree(b->meas.d_ys);
+    src_release(b, -1);
+    (void)be::dfree(b->src.d_rows); (void)be::dfree(b->src.d_ys);
     for (auto &e : b->os.ev) if (e) (void)be::event_destroy(e);
     for (int i = 0; i < acme_batch::NEV; ++i) {
         if (b->ev0[i]) (void)be::event_destroy(b->ev0[i]);
@@ -841,6 +870,7 @@ static int rebuild_on_plain_shape(acme_batch *b) {
     nb->balance = b->balance;
     std::swap(nb->os, b->os);    // (oversampling: factor, taps, the signals' past and scratch go with the instances)
     std::swap(nb->meas, b->meas);    // (measurements: the window's position and the accumulators, too)
+    std::swap(nb->src, b->src);      // (sources: the rows' parameters and the clock)
     std::swap(*b, *nb);          // (b is the plain-shape batch now; the guard destroys what it was)
     return ACME_OK;
 }
@@ -1256,24 +1286,32 @@ static int meas_step(acme_batch *b, const double *y, long long n, long long pitc
     return ACME_OK;
 }
 // u: [N][T][nu], or -- const_mask != 0 -- the varying rows [N][T][nuv] and u_const [N][nu] (acme_batch_run_const); y: [N][T][ny],
-// or NULL (a measured run that stores no outputs)
+// or NULL (a measured run that stores no outputs).  sourced (acme_batch_run_sources): u holds the rows without a source
+// [N][T][nin] (NULL when there is none), the source kernel (acme_source.h) puts the slice's full rows together where the
+// expand kernel does for constant rows, the CONST rows are held, and the source clock advances slice by slice; always
+// sliced -- the batch owns one slice of input rows, never [N][T][nu]
 static int run_os(acme_batch *b, const double *u, const double *u_const, unsigned long long const_mask, double *y, long long T,
-                  int mem, be::stream_t st) {
+                  int mem, be::stream_t st, bool sourced = false) {
     acme_batch::Oversampling &O = b->os;
     acme_batch::Measurement &M = b->meas;
     const int k = O.k, nu = b->P.actual.nu, ny = b->P.actual.ny;
     const size_t N = (size_t)b->N;
     int nin = nu;                               // rows of u as the caller hands them over
-    for (int r = 0; r < nu && r < 64; ++r) nin -= (const_mask >> r & 1ull) ? 1 : 0;
-    const bool host = mem == ACME_MEM_HOST, expand = const_mask != 0ull, keep = y != nullptr;
-    const long long TS = k == 1 && !host && keep ? T : os_slice(T), ns = (T + TS - 1) / TS;
+    if (sourced) const_mask = b->src.cmask;
+    for (int r = 0; r < nu && r < 64; ++r) nin -= ((sourced ? b->src.mask : const_mask) >> r & 1ull) ? 1 : 0;
+    const bool host = mem == ACME_MEM_HOST, expand = !sourced && const_mask != 0ull, keep = y != nullptr;
+    const long long TS = k == 1 && !host && keep && !sourced ? T : os_slice(T), ns = (T + TS - 1) / TS;
     auto len = [&](long long s) { return (s + 1) * TS <= T ? TS : T - s * TS; };
     // (k = 1: the slices of caller's device arrays are packed into d_base when they are not whole)
-    const bool pack = k == 1 && !host && !expand && nu && ns > 1;
+    const bool pack = k == 1 && !host && !expand && !sourced && nu && ns > 1;
+    // (sourced, k = 1, y in device memory: the run kernel writes a slice's outputs packed; they go to y from scratch)
+    const bool scatter = sourced && k == 1 && !host && keep && ny && ns > 1;
+    const bool use_lds = [] { const char *e = getenv("ACME_SOURCE_LDS"); return !(e && e[0] == '0'); }();     // (A/B measurements, tests)
     int rc = ACME_OK;
     if (k > 1) rc = os_grow(&O.d_ou, &O.cap_ou, sizeof(double) * N * (size_t)(k * TS) * nu);
     if (rc == ACME_OK && k > 1) rc = os_grow(&O.d_oy, &O.cap_oy, sizeof(double) * N * (size_t)(k * TS) * ny);
-    if (rc == ACME_OK && (expand || pack)) rc = os_grow(&O.d_base, &O.cap_base, sizeof(double) * N * (size_t)TS * nu);
+    if (rc == ACME_OK && (expand || pack || sourced)) rc = os_grow(&O.d_base, &O.cap_base, sizeof(double) * N * (size_t)TS * nu);
+    if (rc == ACME_OK && scatter) rc = os_grow(&b->src.d_ys, &b->src.cap_ys, sizeof(double) * N * (size_t)TS * ny);
     if (rc == ACME_OK && !keep) rc = os_grow(&M.d_ys, &M.cap_ys, sizeof(double) * N * (size_t)TS * ny);
     if (rc == ACME_OK && host) rc = ensure_staging(b, 2 * sizeof(double) * N * (size_t)TS * nin, keep ? 2 * sizeof(double) * N * (size_t)TS * ny : 0);
     if (rc == ACME_OK && host && expand) rc = os_grow(&b->d_uc, &b->cap_uc, sizeof(double) * N * (size_t)nu);
@@ -1296,9 +1334,17 @@ static int run_os(acme_batch *b, const double *u, const double *u_const, unsigne
             src = O.d_base;
             pitch = n;
         }
+        if (sourced && nu) {
+            SrcArgs A{O.d_base, nin ? src : nullptr, b->src.d_rows, (long long)N, n, n, pitch, b->src.clock, nu, nin, 0, 0ull};
+            src_plan(A, b->src.row, use_lds);
+            HIPCHK(src_launch(A, st));
+            src = O.d_base;
+            pitch = n;
+        }
+        if (sourced) b->src.clock += n;
         // the slice's base-rate outputs
-        double *dst = !keep ? M.d_ys : host ? ybuf(s) : y + (size_t)s * TS * ny;
-        const long long ypitch = keep && !host ? T : n;
+        double *dst = !keep ? M.d_ys : host ? ybuf(s) : scatter ? b->src.d_ys : y + (size_t)s * TS * ny;
+        const long long ypitch = keep && !host && !scatter ? T : n;
         if (k == 1) {
             const int rc_ = launch_run(b, src, dst, n, st, nullptr);
             if (rc_ != ACME_OK) return rc_;
@@ -1321,6 +1367,7 @@ static int run_os(acme_batch *b, const double *u, const double *u_const, unsigne
             }
             O.fresh = false;
         }
+        if (scatter) HIPCHK(src_launch_copy(SrcCopyArgs{y + (size_t)s * TS * ny, dst, (long long)N, n, T, ny}, st));
         return M.on ? meas_step(b, dst, n, ypitch, st) : ACME_OK;
     };
     if (!host) {
@@ -1374,6 +1421,7 @@ int acme_batch_run(acme_batch *b, const double *u, double *y, long long T, int m
     join_worker(b);
     std::unique_lock<std::mutex> serial;           // (the CPU emulator backend is not re-entrant: a worker of
     if (std::mutex *m = be::run_mutex()) serial = std::unique_lock<std::mutex>(*m);   // ANOTHER batch may be running)
+    if (b && b->src.armed) return fail(ACME_ERR_INVALID, "acme_batch_run: input rows have sources (acme_batch_set_source_*); use acme_batch_run_sources");
     return run_impl(b, u, y, T, mem, stream);
 }
 static int run_impl(acme_batch *b, const double *u, double *y, long long T, int mem, void *stream) {
@@ -1607,6 +1655,7 @@ int acme_batch_run_const(acme_batch *b, const double *u_var, const double *u_con
     std::unique_lock<std::mutex> serial;
     if (std::mutex *m = be::run_mutex()) serial = std::unique_lock<std::mutex>(*m);
     if (!b || T < 0) return fail(ACME_ERR_INVALID, "invalid argument to acme_batch_run_const");
+    if (b && b->src.armed) return fail(ACME_ERR_INVALID, "acme_batch_run_const: input rows have sources (acme_batch_set_source_*); use acme_batch_run_sources");
     const int nu = b->P.actual.nu, ny = b->P.actual.ny;
     if (nu > 64) return fail(ACME_ERR_UNSUPPORTED, "acme_batch_run_const: more than 64 input rows");
     const unsigned long long all = nu >= 64 ? ~0ull : ((1ull << nu) - 1ull);
@@ -1727,6 +1776,7 @@ int acme_batch_run_const(acme_batch *b, const double *u_var, const double *u_con
 int acme_batch_run_async(acme_batch *b, const double *u, double *y, long long T, int mem, void *stream) {
     if (!b) return fail(ACME_ERR_INVALID, "null batch");
     join_worker(b);
+    if (b && b->src.armed) return fail(ACME_ERR_INVALID, "acme_batch_run_async: input rows have sources (acme_batch_set_source_*); use acme_batch_run_sources");
     if (b->worker_rc != ACME_OK) {       // a failed asynchronous run nobody waited for: reported now, not dropped
         const int rc = b->worker_rc;
         b->worker_rc = ACME_OK;
@@ -1747,6 +1797,206 @@ int acme_batch_run_async(acme_batch *b, const double *u, double *y, long long T,
     return ACME_OK;
 }
 
+// ---- input rows generated on the device (acme_batch_set_source_*, acme_source.h) --------------------------------------------
+// a per-instance parameter array in device memory; NULL stays NULL (the kind's default for every instance)
+static int src_upload(const void *h, size_t bytes, const void **d) {
+    *d = nullptr;
+    if (!h) return ACME_OK;
+    void *p = nullptr;
+    HIPCHK(be::dmalloc(&p, bytes));
+    const int e = be::copy_h2d(p, h, bytes);
+    if (e != 0) { (void)be::dfree(p); return fail(ACME_ERR_HIP, std::string("copy of source parameters: ") + be::err_string(e)); }
+    *d = p;
+    return ACME_OK;
+}
+// the row's descriptions as the device reads them: the caller's rows numbered in row order
+static int src_commit(acme_batch *b) {
+    acme_batch::Sources &S = b->src;
+    int v = 0;
+    for (int r = 0; r < 64; ++r) S.row[r].var = S.row[r].kind == SRC_NONE ? v++ : 0;
+    if (!S.d_rows) HIPCHK(be::dmalloc((void **)&S.d_rows, sizeof(S.row)));
+    HIPCHK(be::copy_h2d(S.d_rows, S.row, sizeof(S.row)));
+    if (!S.armed) S.clock = 0;
+    return ACME_OK;
+}
+// kind, den (SINE: f_den; TABLE: P), the arrays of the kind (host arrays of N entries, w of P; NULL = default)
+static int set_source(acme_batch *b, int row, int kind, long long den, const long long *f_num, const long long *phase,
+                      const double *w, const double *amp, const double *offset) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const int nu = b->P.actual.nu;
+    if (nu > 64) return fail(ACME_ERR_UNSUPPORTED, "sources: more than 64 input rows");
+    if (row < 0 || row >= nu) return fail(ACME_ERR_INVALID, "source: row beyond the model's inputs");
+    const size_t N = (size_t)b->N;
+    if (kind == SRC_SINE) {
+        if (den <= 0 || den >= (1ll << 31)) return fail(ACME_ERR_INVALID, "sine source: f_den must be 1 ... 2^31 - 1");
+        for (size_t i = 0; i < N; ++i)
+            if ((f_num && (f_num[i] < 0 || f_num[i] >= den)) || (phase && (phase[i] < 0 || phase[i] >= den)))
+                return fail(ACME_ERR_INVALID, "sine source: f_num and phase must be 0 ... f_den - 1 (instance " + std::to_string(i) + ")");
+    }
+    if (kind == SRC_TABLE) {
+        if (den < 1 || den > SRC_MAX_TABLE) return fail(ACME_ERR_INVALID, "table source: P must be 1 ... 2^24");
+        if (!w) return fail(ACME_ERR_INVALID, "table source: null table");
+    }
+    for (size_t i = 0; i < N; ++i)
+        if ((amp && !std::isfinite(amp[i])) || (offset && !std::isfinite(offset[i])))
+            return fail(ACME_ERR_INVALID, "source: non-finite amp or offset (instance " + std::to_string(i) + ")");
+    if (b->iso_thr > 0.0)
+        return fail(ACME_ERR_UNSUPPORTED, "sources are not available while the isolation of slow instances is in force");
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());          // (a launch still in flight may read the row's parameters)
+    // everything is uploaded before the batch is touched: a failure leaves the row as it was
+    SrcRow R{};
+    R.kind = kind;
+    R.den = kind == SRC_CONST ? 1 : den;
+    int rc = src_upload(offset, sizeof(double) * N, (const void **)&R.off);
+    if (rc == ACME_OK && kind != SRC_CONST) rc = src_upload(amp, sizeof(double) * N, (const void **)&R.amp);
+    if (rc == ACME_OK && kind == SRC_SINE) rc = src_upload(f_num, sizeof(long long) * N, (const void **)&R.fnum);
+    if (rc == ACME_OK && kind == SRC_SINE) rc = src_upload(phase, sizeof(long long) * N, (const void **)&R.phase);
+    if (rc == ACME_OK && kind == SRC_TABLE) rc = src_upload(w, sizeof(double) * (size_t)den, (const void **)&R.w);
+    for (auto &e : b->os.ev) if (rc == ACME_OK && !e && be::event_create(&e) != 0) rc = fail(ACME_ERR_HIP, "hipEventCreate");      // (the host pipeline of run_os)
+    if (rc != ACME_OK) {
+        (void)be::dfree(const_cast<double *>(R.amp)); (void)be::dfree(const_cast<double *>(R.off)); (void)be::dfree(const_cast<double *>(R.w));
+        (void)be::dfree(const_cast<long long *>(R.fnum)); (void)be::dfree(const_cast<long long *>(R.phase));
+        return rc;
+    }
+    acme_batch::Sources &S = b->src;
+    const bool first = S.armed == 0;
+    src_release(b, row);
+    S.row[row] = R;
+    S.mask |= 1ull << row;
+    if (kind == SRC_CONST) S.cmask |= 1ull << row;
+    ++S.armed;
+    if (first) S.clock = 0;
+    return src_commit(b);
+}
+
+int acme_batch_set_source_const(acme_batch *b, int row, const double *offset) {
+    return set_source(b, row, SRC_CONST, 1, nullptr, nullptr, nullptr, nullptr, offset);
+}
+int acme_batch_set_source_sine(acme_batch *b, int row, long long f_den, long long *f_num, long long *phase, const double *amp,
+                               const double *offset) {
+    return set_source(b, row, SRC_SINE, f_den, f_num, phase, nullptr, amp, offset);
+}
+int acme_batch_set_source_table(acme_batch *b, int row, const double *w, long long P, const double *amp, const double *offset) {
+    return set_source(b, row, SRC_TABLE, P, nullptr, nullptr, w, amp, offset);
+}
+
+int acme_batch_clear_source(acme_batch *b, int row) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    if (row >= b->P.actual.nu || row >= 64) return fail(ACME_ERR_INVALID, "source: row beyond the model's inputs");
+    if (!b->src.armed) return ACME_OK;
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    src_release(b, row);
+    return src_commit(b);
+}
+
+int acme_batch_set_source_clock(acme_batch *b, long long n) {
+    join_worker(b);
+    if (!b || n < 0) return fail(ACME_ERR_INVALID, "invalid argument to acme_batch_set_source_clock");
+    if (!b->src.armed) return fail(ACME_ERR_INVALID, "no input row has a source");
+    b->src.clock = n;
+    return ACME_OK;
+}
+
+int acme_batch_get_source_clock(acme_batch *b, long long *n) {
+    join_worker(b);
+    if (!b || !n) return fail(ACME_ERR_INVALID, "null argument");
+    if (!b->src.armed) return fail(ACME_ERR_INVALID, "no input row has a source");
+    *n = b->src.clock;
+    return ACME_OK;
+}
+
+static int run_sources_impl(acme_batch *b, const double *u_var, double *y, long long T, int mem, void *stream) {
+    if (!b || T < 0) return fail(ACME_ERR_INVALID, "invalid argument to acme_batch_run_sources");
+    const acme_batch::Sources &S = b->src;
+    if (!S.armed) return fail(ACME_ERR_INVALID, "acme_batch_run_sources: no input row has a source");
+    const int nu = b->P.actual.nu, ny = b->P.actual.ny;
+    if ((nu > S.armed && T > 0 && !u_var) || (ny > 0 && T > 0 && !y && !b->meas.on)) return fail(ACME_ERR_INVALID, "null u_var or y");
+    if (mem != ACME_MEM_HOST && mem != ACME_MEM_DEVICE) return fail(ACME_ERR_INVALID, "mem must be ACME_MEM_HOST or ACME_MEM_DEVICE");
+    if (T > LLONG_MAX - S.clock) return fail(ACME_ERR_INVALID, "acme_batch_run_sources: the source clock would overflow");
+    if (T == 0) return ACME_OK;
+    ON_DEVICE(b);
+    return run_os(b, u_var, nullptr, 0ull, y, T, mem, (be::stream_t)stream, true);
+}
+
+int acme_batch_run_sources(acme_batch *b, const double *u_var, double *y, long long T, int mem, void *stream) {
+    join_worker(b);
+    std::unique_lock<std::mutex> serial;
+    if (std::mutex *m = be::run_mutex()) serial = std::unique_lock<std::mutex>(*m);
+    return run_sources_impl(b, u_var, y, T, mem, stream);
+}
+
+int acme_batch_run_sources_async(acme_batch *b, const double *u_var, double *y, long long T, int mem, void *stream) {
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    join_worker(b);
+    if (b->worker_rc != ACME_OK) {       // (as acme_batch_run_async)
+        const int rc = b->worker_rc;
+        b->worker_rc = ACME_OK;
+        return fail(rc, "previous asynchronous run failed: " + b->worker_err);
+    }
+    b->worker_err.clear();
+    try {
+        b->worker = std::thread([=]() {
+            std::unique_lock<std::mutex> serial;
+            if (std::mutex *m = be::run_mutex()) serial = std::unique_lock<std::mutex>(*m);
+            b->worker_rc = run_sources_impl(b, u_var, y, T, mem, stream);
+            if (b->worker_rc != ACME_OK) b->worker_err = g_err;
+        });
+    } catch (const std::exception &e) {
+        return fail(ACME_ERR_HIP, std::string("cannot start the worker thread: ") + e.what());
+    }
+    return ACME_OK;
+}
+
+// the input a source run of T samples would feed from the current clock, slice by slice: the source kernel writes into the
+// caller's device array, or into one slice of scratch that is copied out (host arrays; the caller's rows staged likewise)
+int acme_batch_render_sources(acme_batch *b, const double *u_var, double *u_out, long long T, int mem, void *stream) {
+    join_worker(b);
+    std::unique_lock<std::mutex> serial;
+    if (std::mutex *m = be::run_mutex()) serial = std::unique_lock<std::mutex>(*m);
+    if (!b || T < 0 || (T > 0 && !u_out)) return fail(ACME_ERR_INVALID, "invalid argument to acme_batch_render_sources");
+    acme_batch::Sources &S = b->src;
+    if (!S.armed) return fail(ACME_ERR_INVALID, "acme_batch_render_sources: no input row has a source");
+    if (mem != ACME_MEM_HOST && mem != ACME_MEM_DEVICE) return fail(ACME_ERR_INVALID, "mem must be ACME_MEM_HOST or ACME_MEM_DEVICE");
+    if (T > LLONG_MAX - S.clock) return fail(ACME_ERR_INVALID, "acme_batch_render_sources: the source clock would overflow");
+    if (T == 0) return ACME_OK;
+    ON_DEVICE(b);
+    const be::stream_t st = (be::stream_t)stream;
+    const int nu = b->P.actual.nu, nin = nu - S.armed;
+    const size_t N = (size_t)b->N;
+    const bool host = mem == ACME_MEM_HOST, var = nin > 0 && u_var;
+    const long long TS = os_slice(T);
+    const bool use_lds = [] { const char *e = getenv("ACME_SOURCE_LDS"); return !(e && e[0] == '0'); }();
+    if (host) {
+        HIPCHK(be::device_sync());          // (a run still in flight on another stream may use the scratch)
+        int rc = os_grow(&b->os.d_base, &b->os.cap_base, sizeof(double) * N * (size_t)TS * nu);
+        if (rc == ACME_OK && var) rc = ensure_staging(b, sizeof(double) * N * (size_t)TS * nin, 0);
+        if (rc != ACME_OK) return rc;
+    }
+    for (long long t0 = 0; t0 < T; t0 += TS) {
+        const long long n = T - t0 < TS ? T - t0 : TS;
+        const double *uv = nullptr;
+        if (var && host) {
+            const size_t w = sizeof(double) * (size_t)n * nin;
+            HIPCHK(be::copy2d_h2d_async(b->d_u, w, u_var + (size_t)t0 * nin, sizeof(double) * (size_t)T * nin, w, N, st));
+            uv = b->d_u;
+        } else if (var)
+            uv = u_var + (size_t)t0 * nin;
+        SrcArgs A{host ? b->os.d_base : u_out + (size_t)t0 * nu, uv, S.d_rows, (long long)N, n, host ? n : T, host ? n : T, S.clock + t0, nu, nin, 0, 0ull};
+        src_plan(A, S.row, use_lds);
+        HIPCHK(src_launch(A, st));
+        if (host) {
+            const size_t w = sizeof(double) * (size_t)n * nu;
+            HIPCHK(be::copy2d_d2h_async(u_out + (size_t)t0 * nu, sizeof(double) * (size_t)T * nu, b->os.d_base, w, w, N, st));
+            HIPCHK(be::stream_sync(st));          // (the scratch is the next slice's)
+        }
+    }
+    return ACME_OK;
+}
+
 int acme_batch_set_isolation(acme_batch *b, double iters_per_sample) {
     join_worker(b);
     if (!b || !(iters_per_sample >= 0.0)) return fail(ACME_ERR_INVALID, "invalid argument to acme_batch_set_isolation");
@@ -1754,6 +2004,8 @@ int acme_batch_set_isolation(acme_batch *b, double iters_per_sample) {
         return fail(ACME_ERR_UNSUPPORTED, "isolation of slow instances is not available on an oversampled batch");
     if (iters_per_sample > 0.0 && b->meas.on)
         return fail(ACME_ERR_UNSUPPORTED, "isolation of slow instances is not available while a measurement is armed");
+    if (iters_per_sample > 0.0 && b->src.armed)
+        return fail(ACME_ERR_UNSUPPORTED, "isolation of slow instances is not available while input rows have sources");
     ON_DEVICE(b);
     HIPCHK(be::device_sync());
     b->iso_thr = iters_per_sample;

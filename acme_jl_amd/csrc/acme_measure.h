@@ -51,11 +51,17 @@ struct MeasTwArgs {
 
 // cos / sin of 2 pi ((h f_num m) mod f_den) / f_den, the phase reduced exactly (h <= 32, f_den < 2^31: products < 2^62)
 // and taken to (-pi, pi] before the one rounding of the angle
+// the angle 2 pi k / f_den of a reduced phase 0 <= k < f_den < 2^31, taken to (-pi, pi] first: two roundings, the quotient's
+// and the product's (shared with the sine sources of acme_source.h)
+ACME_HD inline double phase_angle(long long k, long long f_den) {
+    if (2 * k > f_den) k -= f_den;
+    return 6.283185307179586476925286766559 * ((double)k / (double)f_den);
+}
+
 ACME_HD inline void meas_twiddle(long long h, long long m, long long f_num, long long f_den, double *c, double *s) {
     const long long a = (h * f_num) % f_den;
-    long long k = (a * (m % f_den)) % f_den;
-    if (2 * k > f_den) k -= f_den;
-    const double th = 6.283185307179586476925286766559 * ((double)k / (double)f_den);
+    const long long k = (a * (m % f_den)) % f_den;
+    const double th = phase_angle(k, f_den);
     *c = cos(th);
     *s = sin(th);
 }

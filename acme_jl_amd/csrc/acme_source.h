@@ -1,0 +1,271 @@
+// acme_source.h -- input signals generated on the device (acme_batch_set_source_*): an input row with a source needs no
+// u from the caller -- its value at clock n (base-rate samples since the first source was armed) for instance i is
+//
+//   CONST   offset_i
+//   SINE    fma(amp_i, sin(th), offset_i),  th = 2 pi kappa / f_den,  kappa = (f_num_i n + phase_i) mod f_den taken to
+//           (-f_den / 2, f_den / 2]: the phase reduced exactly in 64-bit integers, the angle formed as meas_twiddle forms
+//           it (phase_angle, acme_measure.h)
+//   TABLE   fma(amp_i, w[n mod P], offset_i)
+//
+// One launch per time slice (acme_api.inc run_os, where the expand kernel sits for constant rows) writes the slice's full
+// [N][len][nu] block: sourced rows generated, the others gathered from the caller's rows.
+//
+// A block takes SRC_INST instances x one tile of SRC_TILE samples; per instance the tile's (sample, row) elements are
+// contiguous, and the threads walk them side by side: a thread keeps ONE row (two neighbouring elements where 16-byte
+// stores are possible: rows r, r + 1 of a sample when nu is even, samples t, t + 1 when nu = 1) and steps dt samples per
+// iteration, so a wave's store is one contiguous run.  What depends on the row only (the clock reduced mod f_den / P, the
+// step dt mod f_den) is computed once per thread; per instance a thread reads its row's parameters once and reduces
+// kappa = (f_num_i m0 + phase_i) mod f_den and the step (f_num_i dt) mod f_den exactly (operands below 2^31: products
+// below 2^62); from there kappa += step with one conditional subtraction per sample -- the integers are exact, so every
+// sample's kappa is the closed form's.  Table rows: the tile's window of w (min(tile, P) entries, the same for every
+// instance) is staged in LDS once per block while the rows' windows fit SRC_LDS doubles; rows beyond that read w from
+// HBM / L2.
+//
+// The per-thread functions are host + device code; the launchers below are __global__ launches under hipcc and plain
+// loops over (block, thread) otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with
+// g++): both run the same index arithmetic.
+#pragma once
+#include <cmath>
+#include <cstdint>
+#include <vector>
+
+#include "acme_common.h"
+#include "acme_measure.h"
+
+namespace acme {
+
+constexpr int SRC_NONE = 0, SRC_CONST = 1, SRC_SINE = 2, SRC_TABLE = 3;      // (include/acme_hip.h: ACME_SOURCE_*)
+constexpr long long SRC_MAX_TABLE = 1ll << 24;
+constexpr int SRC_BLOCK = 256;              // threads per block
+constexpr int SRC_TILE = 4096;              // samples per block
+constexpr int SRC_INST = 4;                 // instances per block
+constexpr int SRC_LDS = 4096;               // doubles of LDS for the table rows' windows (32 KB)
+
+// one input row (an array of 64 in device memory; the per-instance arrays [n], NULL = the default for every instance)
+struct SrcRow {
+    int kind;                   // SRC_*; SRC_NONE: the caller's row
+    int var;                    // SRC_NONE: the row's place among the caller's rows
+    long long den;              // SINE: f_den; TABLE: P
+    const double *amp, *off;    // default 1, 0
+    const long long *fnum, *phase;      // default 0, 0
+    const double *w;            // TABLE: [P]
+};
+
+struct SrcArgs {
+    double *dst;                // instance i, sample t, row r at dst[(i * dpitch + t) * nu + r]
+    const double *uv;           // the caller's rows: uv[(i * upitch + t) * nin + v]; NULL: zeros
+    const SrcRow *rows;         // [nu] (nu <= 64)
+    long long n, len, dpitch, upitch;
+    long long n0;               // the clock at the slice's first sample
+    int nu, nin;
+    int vec;                    // 16-byte stores: nu even, or nu = 1 with len and dpitch even; dst 16-byte aligned
+    unsigned long long lds_rows;        // the table rows whose windows are staged in LDS
+};
+
+struct alignas(16) SrcPair { double a, b; };
+
+// the first entry of w a tile needs: (n0 + tb) mod P
+ACME_HD inline unsigned long long src_table_base(const SrcArgs &A, long long P, long long tb) {
+    return ((unsigned long long)(A.n0 % P) + (unsigned long long)tb) % (unsigned long long)P;
+}
+// a table row's window in LDS: offset (the windows of the staged rows before it) and length for a tile of tl samples
+ACME_HD inline int src_lds_offset(const SrcArgs &A, int row) {
+    const long long tmax = A.len < SRC_TILE ? A.len : SRC_TILE;
+    long long off = 0;
+    for (int r = 0; r < row; ++r)
+        if (A.lds_rows >> r & 1ull) off += A.rows[r].den < tmax ? A.rows[r].den : tmax;
+    return (int)off;
+}
+
+// the block's windows: lds[off + q] = w[(base + q) mod P], q < min(tl, P)
+ACME_HD inline void src_stage(const SrcArgs &A, long long by, int tid, double *lds) {
+    const long long tb = by * SRC_TILE, tl = A.len - tb < SRC_TILE ? A.len - tb : SRC_TILE;
+    for (int r = 0; r < A.nu; ++r) {
+        if (!(A.lds_rows >> r & 1ull)) continue;
+        const SrcRow &R = A.rows[r];
+        const long long P = R.den, win = P < tl ? P : tl;
+        const long long base = (long long)src_table_base(A, P, tb);
+        double *o = lds + src_lds_offset(A, r);
+        for (long long q = tid; q < win; q += SRC_BLOCK) {
+            const long long j = base + q;                   // < 2 P
+            o[q] = R.w[j >= P ? j - P : j];
+        }
+    }
+}
+
+// what a thread keeps of one of its rows: everything that does not depend on the instance ...
+struct SrcSlot {
+    int kind, var;
+    unsigned long long den;     // SINE: f_den; TABLE: the index's modulus (the window's length, or P from HBM)
+    unsigned long long m0;      // SINE: (n0 + first sample) mod f_den; TABLE: the first sample's index
+    unsigned long long dstep;   // dt mod den
+    const double *amp, *off, *tab;
+    const long long *fnum, *phase;
+};
+// ... and the instance's: parameters, the running phase / index and its step
+struct SrcRun {
+    double amp, off;
+    unsigned long long k, step;
+    const double *u;            // SRC_NONE: the caller's row at the thread's next sample
+};
+
+// row `row`, first sample tb + ts of the slice, dt samples per step
+ACME_HD inline void src_slot_init(const SrcArgs &A, int row, long long tb, long long tl, long long ts, long long dt, const double *lds,
+                                  SrcSlot &S) {
+    const SrcRow &R = A.rows[row];
+    S.kind = R.kind; S.var = R.var;
+    S.amp = R.amp; S.off = R.off; S.fnum = R.fnum; S.phase = R.phase; S.tab = R.w;
+    S.den = 1; S.m0 = 0; S.dstep = 0;
+    if (R.kind == SRC_SINE) {
+        S.den = (unsigned long long)R.den;
+        S.m0 = ((unsigned long long)(A.n0 % R.den) + (unsigned long long)(tb + ts)) % S.den;      // (n mod f_den first)
+        S.dstep = (unsigned long long)dt % S.den;
+    } else if (R.kind == SRC_TABLE) {
+        if (A.lds_rows >> row & 1ull) {
+            S.den = (unsigned long long)(R.den < tl ? R.den : tl);
+            S.m0 = (unsigned long long)ts % S.den;
+            S.tab = lds + src_lds_offset(A, row);
+        } else {
+            S.den = (unsigned long long)R.den;
+            S.m0 = (src_table_base(A, R.den, tb) + (unsigned long long)ts) % S.den;
+        }
+        S.dstep = (unsigned long long)dt % S.den;
+    }
+}
+
+ACME_HD inline void src_run_init(const SrcArgs &A, const SrcSlot &S, long long i, long long tb, long long ts, SrcRun &R) {
+    R.amp = S.amp ? S.amp[i] : 1.0;
+    R.off = S.off ? S.off[i] : 0.0;
+    R.k = S.m0;
+    R.step = S.dstep;
+    R.u = nullptr;
+    if (S.kind == SRC_SINE) {
+        const unsigned long long f = S.fnum ? (unsigned long long)S.fnum[i] : 0ull, p = S.phase ? (unsigned long long)S.phase[i] : 0ull;
+        R.k = (f * S.m0 + p) % S.den;               // f, m0, p < f_den < 2^31
+        R.step = (f * S.dstep) % S.den;
+    } else if (S.kind == SRC_NONE && A.uv)
+        R.u = A.uv + (i * A.upitch + tb + ts) * A.nin + S.var;
+}
+
+// the row's value at the thread's current sample; on to the next (dt samples later)
+ACME_HD inline double src_next(const SrcSlot &S, SrcRun &R, long long ustep) {
+    double v;
+    if (S.kind == SRC_CONST) return R.off;
+    if (S.kind == SRC_NONE) {
+        if (!R.u) return 0.0;
+        v = *R.u;
+        R.u += ustep;
+        return v;
+    }
+    if (S.kind == SRC_SINE) v = fma(R.amp, sin(phase_angle((long long)R.k, (long long)S.den)), R.off);
+    else v = fma(R.amp, S.tab[R.k], R.off);
+    R.k += R.step;
+    if (R.k >= S.den) R.k -= S.den;
+    return v;
+}
+
+// thread tid of block (bx, by): instances bx SRC_INST ..., samples by SRC_TILE ...
+ACME_HD inline void src_thread(const SrcArgs &A, long long bx, long long by, int tid, const double *lds) {
+    const int nu = A.nu;
+    const long long tb = by * SRC_TILE, tl = A.len - tb < SRC_TILE ? A.len - tb : SRC_TILE;
+    // the thread's elements: row r0 (and its neighbour) of samples ts, ts + dt, ...
+    int r0, r1;
+    long long ts, ts1, dt;
+    if (A.vec && nu == 1) {
+        r0 = r1 = 0; ts = 2 * tid; ts1 = ts + 1; dt = 2 * SRC_BLOCK;
+    } else {
+        const int per = A.vec ? nu / 2 : nu, act = SRC_BLOCK / per * per;        // units per sample; threads in use
+        if (tid >= act) return;
+        r0 = A.vec ? 2 * (tid % per) : tid % per;
+        r1 = r0 + 1;
+        ts = ts1 = tid / per;
+        dt = act / per;
+    }
+    SrcSlot s0, s1;
+    src_slot_init(A, r0, tb, tl, ts, dt, lds, s0);
+    if (A.vec) src_slot_init(A, r1, tb, tl, ts1, dt, lds, s1);
+    const long long ustep = dt * A.nin;
+    for (long long i = bx * SRC_INST; i < (bx + 1) * SRC_INST && i < A.n; ++i) {
+        SrcRun q0, q1;
+        src_run_init(A, s0, i, tb, ts, q0);
+        double *d = A.dst + (i * A.dpitch + tb) * nu;
+        if (A.vec) {
+            src_run_init(A, s1, i, tb, ts1, q1);
+            for (long long t = ts; t < tl; t += dt) {
+                const SrcPair v{src_next(s0, q0, ustep), src_next(s1, q1, ustep)};
+                *reinterpret_cast<SrcPair *>(d + t * nu + r0) = v;
+            }
+        } else {
+            for (long long t = ts; t < tl; t += dt) d[t * nu + r0] = src_next(s0, q0, ustep);
+        }
+    }
+}
+
+// the launch's shape: which table rows are staged in LDS (in row order while their windows fit; use_lds false: none) and
+// whether 16-byte stores are possible
+inline void src_plan(SrcArgs &A, const SrcRow *host_rows, bool use_lds) {
+    const long long tmax = A.len < SRC_TILE ? A.len : SRC_TILE;
+    long long used = 0;
+    A.lds_rows = 0ull;
+    for (int r = 0; r < A.nu && use_lds; ++r) {
+        if (host_rows[r].kind != SRC_TABLE) continue;
+        const long long win = host_rows[r].den < tmax ? host_rows[r].den : tmax;
+        if (used + win > SRC_LDS) break;
+        A.lds_rows |= 1ull << r;
+        used += win;
+    }
+    const bool even = A.nu % 2 == 0 || (A.nu == 1 && A.len % 2 == 0 && A.dpitch % 2 == 0);
+    A.vec = even && (uintptr_t)A.dst % 16 == 0 ? 1 : 0;
+}
+
+// packed outputs of a slice -> the caller's array: dst[(i * pitch + t) * rows + r] = src[(i * len + t) * rows + r]
+struct SrcCopyArgs { double *dst; const double *src; long long n, len, pitch; int rows; };
+ACME_HD inline void src_copy(const SrcCopyArgs &A, long long idx) {
+    const long long w = A.len * A.rows, i = idx / w, e = idx - i * w;
+    A.dst[i * A.pitch * A.rows + e] = A.src[idx];
+}
+
+}  // namespace acme
+
+// ---- launchers ---------------------------------------------------------------------------------------------------------
+#if defined(__HIPCC__)
+__global__ __launch_bounds__(acme::SRC_BLOCK) void acme_source_kernel(acme::SrcArgs A) {
+    __shared__ double lds[acme::SRC_LDS];
+    if (A.lds_rows) {           // (uniform over the launch)
+        acme::src_stage(A, blockIdx.y, threadIdx.x, lds);
+        __syncthreads();
+    }
+    acme::src_thread(A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+__global__ __launch_bounds__(256) void acme_source_copy_kernel(acme::SrcCopyArgs A) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx < A.n * A.len * A.rows) acme::src_copy(A, idx);
+}
+namespace acme {
+inline int src_launch(const SrcArgs &A, hipStream_t st) {
+    const dim3 grid((unsigned)((A.n + SRC_INST - 1) / SRC_INST), (unsigned)((A.len + SRC_TILE - 1) / SRC_TILE));
+    hipLaunchKernelGGL(acme_source_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
+    return (int)hipGetLastError();
+}
+inline int src_launch_copy(const SrcCopyArgs &A, hipStream_t st) {
+    hipLaunchKernelGGL(acme_source_copy_kernel, dim3((unsigned)((A.n * A.len * A.rows + 255) / 256)), dim3(256), 0, st, A);
+    return (int)hipGetLastError();
+}
+}  // namespace acme
+#else
+namespace acme {
+inline int src_launch(const SrcArgs &A, void *) {
+    std::vector<double> lds(SRC_LDS);
+    for (long long by = 0; by * SRC_TILE < A.len; ++by) {
+        for (int tid = 0; tid < SRC_BLOCK && A.lds_rows; ++tid) src_stage(A, by, tid, lds.data());
+        for (long long bx = 0; bx * SRC_INST < A.n; ++bx)
+            for (int tid = 0; tid < SRC_BLOCK; ++tid) src_thread(A, bx, by, tid, lds.data());
+    }
+    return 0;
+}
+inline int src_launch_copy(const SrcCopyArgs &A, void *) {
+    for (long long idx = 0; idx < A.n * A.len * A.rows; ++idx) src_copy(A, idx);
+    return 0;
+}
+}  // namespace acme
+#endif

@@ -122,6 +122,24 @@ def birdie(vol=None):
     ])
 
 
+def level_sweep_thd(model, levels, consts=(), f0=(10, 441), fs=44100, seconds=1, settle=1, harmonics=8, signal_row=0, device=None):
+    """THD against input level with nothing but parameters going in and results coming out: a sine source of
+    ``f0 = (num, den)`` x the sample rate ``fs`` at ``levels`` (one instance each) on ``signal_row``, the other input rows held at
+    ``consts`` ({row: value or N values}), ``settle`` seconds unmeasured, then ``seconds`` measured -- no u, no y
+    (``ModelRunner.set_source`` / ``measure``).  Returns (thd [N], Measurement).  Needs a GPU."""
+    import numpy as np
+    from .runner import ModelRunner
+    levels = np.asarray(levels, dtype=np.float64)
+    r = ModelRunner(model, len(levels), device=device)
+    r.set_source(signal_row, "sine", amp=levels, f_den=f0[1], f_num=f0[0])
+    for row, value in dict(consts).items():
+        r.set_source(row, "const", offset=value)
+    r.set_measurement(start=settle * fs, length=seconds * fs, f0=tuple(f0), harmonics=harmonics)
+    r.measure(T=(settle + seconds) * fs)
+    m = r.measurement()
+    return m.thd()[:, 0], m
+
+
 def sallenkey():
     return build([
         ("j_in", voltagesource(), {"-": "gnd"}),

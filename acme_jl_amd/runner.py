@@ -60,7 +60,14 @@ ABI_SYMBOLS = [
     "acme_batch_set_resabstol", "acme_batch_get_state", "acme_batch_set_state",
     "acme_oversampling_design", "acme_batch_set_oversampling",
     "acme_batch_set_measurement", "acme_batch_clear_measurement", "acme_batch_reset_measurement", "acme_batch_get_measurement",
+    "acme_batch_set_source_const", "acme_batch_set_source_sine", "acme_batch_set_source_table", "acme_batch_clear_source",
+    "acme_batch_set_source_clock", "acme_batch_get_source_clock", "acme_batch_run_sources", "acme_batch_run_sources_async",
+    "acme_batch_render_sources",
 ]
+
+SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE = 1, 2, 3
+_SOURCE_KINDS = {"const": SOURCE_CONST, "sine": SOURCE_SINE, "table": SOURCE_TABLE,
+                 SOURCE_CONST: SOURCE_CONST, SOURCE_SINE: SOURCE_SINE, SOURCE_TABLE: SOURCE_TABLE}
 
 
 def _preload_torch_hip_runtime():
@@ -143,6 +150,16 @@ class Library:
         L.acme_batch_clear_measurement.argtypes = [vp]
         L.acme_batch_reset_measurement.argtypes = [vp]
         L.acme_batch_get_measurement.argtypes = [vp, dp, C.POINTER(C.c_longlong)]
+        lp = C.POINTER(C.c_longlong)
+        L.acme_batch_set_source_const.argtypes = [vp, C.c_int, dp]
+        L.acme_batch_set_source_sine.argtypes = [vp, C.c_int, C.c_longlong, lp, lp, dp, dp]
+        L.acme_batch_set_source_table.argtypes = [vp, C.c_int, dp, C.c_longlong, dp, dp]
+        L.acme_batch_clear_source.argtypes = [vp, C.c_int]
+        L.acme_batch_set_source_clock.argtypes = [vp, C.c_longlong]
+        L.acme_batch_get_source_clock.argtypes = [vp, lp]
+        L.acme_batch_run_sources.argtypes = [vp, vp, vp, C.c_longlong, C.c_int, vp]
+        L.acme_batch_run_sources_async.argtypes = [vp, vp, vp, C.c_longlong, C.c_int, vp]
+        L.acme_batch_render_sources.argtypes = [vp, vp, vp, C.c_longlong, C.c_int, vp]
 
     def check(self, rc):
         if rc < 0:
@@ -325,6 +342,7 @@ class ModelRunner:
         self._warned = 0
         self._os = (1, 1, 1)            # oversampling: factor, interpolation taps, decimation taps
         self._meas = None               # measurement: (harmonics, measured rows) while armed
+        self._sources = {}              # input row -> kind, while the row has a source
         self._progress_cb = None
         if showprogress:
             fn = showprogress if callable(showprogress) else _print_progress
@@ -413,10 +431,15 @@ class ModelRunner:
         self.lib.check(self.lib.L.acme_batch_get_measurement(self.h, _dp(out), C.byref(count)))
         return Measurement(out, count.value, rows)
 
-    def measure(self, u, check=True, time_major=False):
+    def measure(self, u=None, check=True, time_major=False, T=None):
         """``run`` without outputs: advance the instances over ``u`` (shapes as ``run``) and only feed the armed
-        measurement (y = NULL: nothing of y is stored or copied).  Returns ``self``; ``measurement()`` reads the results."""
+        measurement (y = NULL: nothing of y is stored or copied).  Returns ``self``; ``measurement()`` reads the results.
+        ``u=None`` when every input row has a source (``set_source``): ``T`` samples are generated on the device."""
         m = self.model
+        if u is None:
+            if T is None or len(self._sources) != m.nu:
+                raise DimensionMismatch("measure(u=None) needs a source on every input row and the number of samples T")
+            return self.run_sources(T, y=False, check=check)
         u = np.asarray(u, dtype=np.float64)
         if not time_major:
             if u.ndim == 2 and self.n == 1:
@@ -436,6 +459,135 @@ class ModelRunner:
     def measure_const(self, u_var, u_const, const_rows, check=True):
         """``run_const`` without outputs (y = NULL): only the armed measurement is fed.  Returns ``self``."""
         return self.run_const(u_var, u_const, const_rows, y=False, check=check)
+
+    # ---- sources: input rows generated on the device ------------------------------------------
+    def _per_instance(self, a, dtype, what):
+        """a per-instance parameter (None, a scalar or N values) as the ABI takes it: (array kept alive, pointer)"""
+        if a is None:
+            return None, None
+        arr = np.ascontiguousarray(np.broadcast_to(np.asarray(a, dtype=dtype), (self.n,)))
+        if dtype is np.int64 and not np.all(arr == np.asarray(a)):
+            raise DimensionMismatch(f"{what} must be integers")
+        return arr, arr.ctypes.data_as(C.POINTER(C.c_double if dtype is np.float64 else C.c_longlong))
+
+    def set_source(self, row, kind, amp=None, offset=None, f_den=None, f_num=None, phase=None, table=None):
+        """Give input row ``row`` a source (``acme_batch_set_source_*``): the library generates the row on the device, at
+        source clock n (base-rate samples since the first source was armed) for instance i
+
+        * ``"const"``: ``offset[i]``
+        * ``"sine"``: ``fma(amp[i], sin(2 pi kappa / f_den), offset[i])``, kappa = (f_num[i] n + phase[i]) mod f_den -- the
+          frequency f_num[i] / f_den of the sample rate per instance, the phase reduced exactly in integers
+        * ``"table"``: ``fma(amp[i], table[n mod P], offset[i])``, a looped wavetable of P entries
+
+        ``amp``, ``offset``, ``f_num``, ``phase``: None (amp 1, the others 0), a scalar or N values.  ``run_sources`` then runs
+        without these rows; its results are those of ``run`` on ``render_sources``' array, bit for bit."""
+        k = _SOURCE_KINDS.get(kind)
+        if k is None:
+            raise ValueError(f"unknown source kind {kind!r}: 'const', 'sine' or 'table'")
+        aa, ap = self._per_instance(amp, np.float64, "amp")
+        oa, op = self._per_instance(offset, np.float64, "offset")
+        L = self.lib.L
+        if k == SOURCE_CONST:
+            self.lib.check(L.acme_batch_set_source_const(self.h, int(row), op))
+        elif k == SOURCE_SINE:
+            if f_den is None:
+                raise ValueError("a sine source needs f_den")
+            fa, fp = self._per_instance(f_num, np.int64, "f_num")
+            pa, pp = self._per_instance(phase, np.int64, "phase")
+            self.lib.check(L.acme_batch_set_source_sine(self.h, int(row), int(f_den), fp, pp, ap, op))
+        else:
+            if table is None:
+                raise ValueError("a table source needs a table")
+            w = np.ascontiguousarray(np.asarray(table, dtype=np.float64).ravel())
+            self.lib.check(L.acme_batch_set_source_table(self.h, int(row), _dp(w), len(w), ap, op))
+        self._sources[int(row)] = k
+        return self
+
+    def clear_source(self, row=-1):
+        """the row is the caller's again (``acme_batch_clear_source``); ``row=-1``: every row"""
+        self.lib.check(self.lib.L.acme_batch_clear_source(self.h, int(row)))
+        if row < 0:
+            self._sources = {}
+        else:
+            self._sources.pop(int(row), None)
+        return self
+
+    @property
+    def source_clock(self):
+        """the source clock: base-rate samples the source runs have advanced since the first source was armed"""
+        n = C.c_longlong(0)
+        self.lib.check(self.lib.L.acme_batch_get_source_clock(self.h, C.byref(n)))
+        return n.value
+
+    @source_clock.setter
+    def source_clock(self, n):
+        self.lib.check(self.lib.L.acme_batch_set_source_clock(self.h, int(n)))
+
+    def _u_var(self, u_var, T):
+        """(array or None, pointer, T): the rows without a source, (N, T, nu_var) in the ABI's layout"""
+        nuv = self.model.nu - len(self._sources)
+        if not self._sources:
+            raise AcmeError("no input row has a source (set_source)")
+        if nuv == 0:
+            if u_var is not None and np.asarray(u_var).size:
+                raise DimensionMismatch("every input row has a source: u_var must be None")
+            if T is None:
+                raise DimensionMismatch("every input row has a source: give the number of samples T")
+            return None, None, int(T)
+        if u_var is None:
+            raise DimensionMismatch(f"u_var must have shape ({self.n}, T, {nuv})")
+        u_var = np.ascontiguousarray(u_var, dtype=np.float64)
+        if u_var.ndim != 3 or u_var.shape[0] != self.n or u_var.shape[2] != nuv or (T is not None and T != u_var.shape[1]):
+            raise DimensionMismatch(f"u_var must have shape ({self.n}, T, {nuv})")
+        return u_var, u_var.ctypes.data, u_var.shape[1]
+
+    def run_sources(self, T=None, u_var=None, y=None, check=True):
+        """``run`` with the sourced rows generated on the device (``acme_batch_run_sources``): ``u_var`` (N, T, nu_var) holds
+        only the rows without a source, in row order -- None when every row has one, then ``T`` says how many samples.
+        Returns y (N, T, ny); ``y=False`` while a measurement is armed: nothing of y is stored (returns ``self``)."""
+        u_var, up, T = self._u_var(u_var, T)
+        ny = self.model.ny
+        if y is False:
+            self.lib.check(self.lib.L.acme_batch_run_sources(self.h, up, None, T, ACME_MEM_HOST, None))
+            self._hold(u_var)
+            if check:
+                self.check()
+            return self
+        if y is None:
+            y = np.empty((self.n, T, ny), dtype=np.float64)
+        elif not (isinstance(y, np.ndarray) and y.dtype == np.float64 and y.flags.c_contiguous and y.shape == (self.n, T, ny)):
+            raise DimensionMismatch(f"y must be a C-contiguous float64 array of shape ({self.n}, {T}, {ny})")
+        self.lib.check(self.lib.L.acme_batch_run_sources(self.h, up, y.ctypes.data, T, ACME_MEM_HOST, None))
+        self._hold(u_var, y)
+        if check:
+            self.check()
+        return y
+
+    def run_sources_async(self, T=None, u_var=None, y=None):
+        """``acme_batch_run_sources_async`` on host buffers (shapes as ``run_sources``; ``y=None`` while a measurement is
+        armed: no outputs).  Returns at once; ``wait()`` joins the run.  The caller keeps ``y`` alive until then."""
+        u_var, up, T = self._u_var(u_var, T)
+        if y is not None and not (isinstance(y, np.ndarray) and y.dtype == np.float64 and y.flags.c_contiguous
+                                  and y.shape == (self.n, T, self.model.ny)):
+            raise DimensionMismatch(f"y must be a C-contiguous float64 array of shape ({self.n}, {T}, {self.model.ny})")
+        self._inflight = (u_var, y)
+        self._hold(u_var, y)
+        self.lib.check(self.lib.L.acme_batch_run_sources_async(self.h, up, None if y is None else y.ctypes.data, T,
+                                                               ACME_MEM_HOST, None))
+
+    def render_sources(self, T=None, u_var=None):
+        """The input (N, T, nu) a source run of ``T`` samples would feed from the current clock
+        (``acme_batch_render_sources``): sourced rows generated, the others from ``u_var`` (zeros if None).  Advances
+        neither the clock nor the model."""
+        if u_var is None:
+            if T is None:
+                raise DimensionMismatch("render_sources needs T or u_var")
+            up, T = None, int(T)
+        else:
+            u_var, up, T = self._u_var(u_var, T)
+        out = np.empty((self.n, T, self.model.nu), dtype=np.float64)
+        self.lib.check(self.lib.L.acme_batch_render_sources(self.h, up, out.ctypes.data, T, ACME_MEM_HOST, None))
+        return out
 
     def set_balance(self, mode=-1):
         """Placement of the waves by their measured cost (``acme_batch_set_balance``): -1 the library decides
@@ -821,9 +973,72 @@ class MultiDeviceRunner:
         """the shards' ``Measurement`` results, concatenated along the instances"""
         return Measurement.concatenate([r.measurement() for r in self.runners if r is not None])
 
-    def measure(self, u, check=True):
-        """``run`` with y = NULL on every device (``u``: (N, T, nu), the ABI's layout); only the measurements are fed."""
+    def measure(self, u=None, check=True, T=None):
+        """``run`` with y = NULL on every device (``u``: (N, T, nu), the ABI's layout); only the measurements are fed.
+        ``u=None`` when every input row has a source: ``T`` samples are generated on the devices."""
+        if u is None:
+            return self.run_sources(T, y=False, check=check)
         return self.run(u, y=False, check=check)
+
+    # ---- sources: the per-instance parameters sliced over the devices ---------------------------
+    def set_source(self, row, kind, amp=None, offset=None, f_den=None, f_num=None, phase=None, table=None):
+        """``ModelRunner.set_source`` on every device's batch, each with its instances' parameters"""
+        def part(a, lo, hi):
+            return a if a is None or np.ndim(a) == 0 else np.asarray(a)[lo:hi]
+        for a in (amp, offset, f_num, phase):
+            if a is not None and np.ndim(a) != 0 and len(a) != self.n:
+                raise DimensionMismatch(f"per-instance source parameters need {self.n} values")
+        for r, (lo, hi) in zip(self.runners, self.ranges):
+            if r is not None:
+                r.set_source(row, kind, part(amp, lo, hi), part(offset, lo, hi), f_den, part(f_num, lo, hi), part(phase, lo, hi), table)
+        return self
+
+    def clear_source(self, row=-1):
+        for r in self.runners:
+            if r is not None:
+                r.clear_source(row)
+        return self
+
+    @property
+    def source_clock(self):
+        return next(r for r in self.runners if r is not None).source_clock
+
+    @source_clock.setter
+    def source_clock(self, n):
+        for r in self.runners:
+            if r is not None:
+                r.source_clock = n
+
+    def run_sources(self, T=None, u_var=None, y=None, check=True):
+        """``ModelRunner.run_sources`` on every device at once (``run_sources_async``, then joined): ``u_var`` (N, T, nu_var)
+        or None, returns / fills ``y`` (N, T, ny); ``y=False``: no outputs (measurement armed), returns ``self``."""
+        if u_var is not None:
+            u_var = np.ascontiguousarray(u_var, dtype=np.float64)
+            if u_var.ndim != 3 or u_var.shape[0] != self.n:
+                raise DimensionMismatch(f"u_var must have shape ({self.n}, T, nu_var)")
+            T = u_var.shape[1]
+        if T is None:
+            raise DimensionMismatch("every input row has a source: give the number of samples T")
+        if y is None:
+            y = np.empty((self.n, int(T), self.model.ny), dtype=np.float64)
+        started, err = [], None
+        for r, (lo, hi) in zip(self.runners, self.ranges):
+            if r is not None:
+                r.run_sources_async(T, None if u_var is None else u_var[lo:hi], None if y is False else y[lo:hi])
+                started.append(r)
+        for r in started:
+            try:
+                r.wait(check=check)
+            except AcmeError as e:
+                err = err or e
+        if err is not None:
+            raise err
+        return self if y is False else y
+
+    def render_sources(self, T=None, u_var=None):
+        parts = [r.render_sources(T, None if u_var is None else np.asarray(u_var)[lo:hi])
+                 for r, (lo, hi) in zip(self.runners, self.ranges) if r is not None]
+        return np.concatenate(parts)
 
     def run(self, u, y=None, check=True):
         """``u``: (N, T, nu) C-contiguous float64 (the ABI's layout); returns / fills ``y`` (N, T, ny)."""

@@ -270,6 +270,65 @@ int acme_batch_reset_measurement(acme_batch *b);
  * acme_batch_run_async and synchronises the device. */
 int acme_batch_get_measurement(acme_batch *b, double *out, long long *count);
 
+/* Sources: input signals generated on the device.  In a level sweep, a potentiometer grid, a Monte-Carlo run the input of
+ * instance i is a known function of a few numbers and one shared waveform; a row with a SOURCE needs no u from the caller --
+ * the library generates it time slice by time slice (one slice of scratch; with a measurement armed and y = NULL a sweep owns
+ * no [N][T] array anywhere, and nothing but parameters and results crosses the bus).
+ *   source clock  while at least one row has a source the batch has a clock n (64-bit, base-rate samples): 0 when the first
+ *                 source is armed, advanced by T by every source run, carried from call to call
+ *   kinds         value of the row at clock n, instance i
+ *     ACME_SOURCE_CONST   offset_i
+ *     ACME_SOURCE_SINE    fma(amp_i, sin(th), offset_i),  th = 2 pi kappa / f_den,
+ *                         kappa = (f_num_i n + phase_i) mod f_den taken to (-f_den / 2, f_den / 2]: the phase reduced exactly in
+ *                         64-bit integers (n mod f_den first), the angle with two roundings (the quotient kappa / f_den, its
+ *                         product with 2 pi) as the measurement's twiddles; 0 <= f_num_i, phase_i < f_den < 2^31.  The
+ *                         frequency is f_num_i / f_den x the base sample rate per instance: a frequency sweep is one batch
+ *     ACME_SOURCE_TABLE   fma(amp_i, w[n mod P], offset_i): a looped wavetable w[P], 1 <= P <= ACME_MAX_SOURCE_TABLE (a chirp,
+ *                         a multitone, a recorded bar: P = its length)
+ *   parameters    amp, offset, f_num, phase: HOST arrays of N entries, copied to the device by the call (parameters, not
+ *                 signals); NULL = the same default for every instance (amp 1, the others 0).  w: a host array of P entries.
+ *                 (f_num and phase are only read.)
+ * DEFINING PROPERTY: acme_batch_run_sources produces, bit for bit, what acme_batch_run produces on the materialised u --
+ * what acme_batch_render_sources writes --: outputs, state, extrapolation origins, acme_report, measurement accumulators,
+ * oversampling histories; in host and device memory, with y stored or y = NULL (measurement armed), in split calls (T1 then
+ * T2 = one run of T1 + T2), asynchronously, with the balancing on or off.  On an oversampled batch a sourced row is generated
+ * at the BASE rate and then treated as a caller's row is: interpolated, or held if its bit is in held_rows; a CONST row is
+ * always held (as the constant rows of acme_batch_run_const are).
+ * Runs go slice by slice on the launch stream (the source kernel, csrc/acme_source.h, ahead of the slice's interpolation /
+ * run kernel); host buffers take the staged slice pipeline, never the streamed path of acme_batch_set_host_retention.  While
+ * a row has a source, acme_batch_run, _run_const and _run_async return ACME_ERR_INVALID (rows of a full u would be silently
+ * ignored).  acme_batch_set_matrices, _set_state, _reset_report, _set_oversampling and the measurement calls leave the sources
+ * and the clock alone.  Not together with acme_batch_set_isolation (ACME_ERR_UNSUPPORTED either way round), nor on models of
+ * more than 64 input rows.  No source armed: no launch, allocation or synchronisation of any run changes. */
+#define ACME_SOURCE_CONST 1
+#define ACME_SOURCE_SINE 2
+#define ACME_SOURCE_TABLE 3
+#define ACME_MAX_SOURCE_TABLE 16777216
+/* give input row `row` a source (replacing the one it has).  Validates its arguments (ACME_ERR_INVALID: row beyond the model's
+ * inputs, f_den or P out of range, an f_num_i or phase_i outside 0 ... f_den - 1, non-finite amp / offset).  Completes the
+ * batch's outstanding work first. */
+int acme_batch_set_source_const(acme_batch *b, int row, const double *offset);
+int acme_batch_set_source_sine(acme_batch *b, int row, long long f_den, long long *f_num, long long *phase,
+                               const double *amp, const double *offset);
+int acme_batch_set_source_table(acme_batch *b, int row, const double *w, long long P, const double *amp,
+                                const double *offset);
+/* the row is the caller's again; row < 0: every row.  With the last source the clock goes (the next first source starts
+ * it at 0). */
+int acme_batch_clear_source(acme_batch *b, int row);
+/* the source clock (n >= 0); ACME_ERR_INVALID while no row has a source */
+int acme_batch_set_source_clock(acme_batch *b, long long n);
+int acme_batch_get_source_clock(acme_batch *b, long long *n);
+/* run! with the sourced rows generated: u_var [N][T][nu_var] holds only the rows WITHOUT a source, in row order (the layout
+ * of acme_batch_run_const); NULL when every row has a source.  y, T, mem, stream as acme_batch_run (y = NULL only while a
+ * measurement is armed).  ACME_ERR_INVALID when no row has a source.  The _async form: as acme_batch_run_async, joined by
+ * acme_batch_wait. */
+int acme_batch_run_sources(acme_batch *b, const double *u_var, double *y, long long T, int mem, void *stream);
+int acme_batch_run_sources_async(acme_batch *b, const double *u_var, double *y, long long T, int mem, void *stream);
+/* write the [N][T][nu] input a source run of T samples would feed from the current clock -- sourced rows generated, the
+ * others taken from u_var, zero where u_var is NULL --; advances neither the clock nor the model.  mem / stream: where
+ * u_var and u_out live, as acme_batch_run. */
+int acme_batch_render_sources(acme_batch *b, const double *u_var, double *u_out, long long T, int mem, void *stream);
+
 /* acme_batch_run without blocking the caller: the same run on a worker thread of the library (a
  * host-buffer run drives its time-slice pipeline from there).  ONE host thread can thereby keep one
  * batch per GPU of a node busy -- start all, then acme_batch_wait each -- which is how a single

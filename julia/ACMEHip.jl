@@ -35,7 +35,8 @@ import ACME: run!, solve, hasconverged, needediterations, set_resabstol!,
              get_extrapolation_origin, set_extrapolation_origin, get_extrapolation_jacobian
 
 export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host_buffers!, release_host_buffers!, set_isolation!, set_balance!,
-       MeasureSpec, Measurement, set_measurement!, clear_measurement!, reset_measurement!, measurement, measure!
+       MeasureSpec, Measurement, set_measurement!, clear_measurement!, reset_measurement!, measurement, measure!,
+       set_source!, clear_source!, source_clock, source_clock!, run_sources!, render_sources
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
 
@@ -47,6 +48,8 @@ const ACME_SOLVER_SIMPLE, ACME_SOLVER_HOMOTOPY, ACME_SOLVER_CACHING_HOMOTOPY = C
 const ACME_MEM_HOST, ACME_MEM_DEVICE = Cint(0), Cint(1)
 const ACME_MAX_OVERSAMPLING = 16
 const ACME_MAX_HARMONICS = 32
+const ACME_SOURCE_CONST, ACME_SOURCE_SINE, ACME_SOURCE_TABLE = Cint(1), Cint(2), Cint(3)
+const ACME_MAX_SOURCE_TABLE = 16777216
 const KIND_NQ = Dict(1 => 2, 2 => 4, 3 => 5, 4 => 3, 5 => 2, 6 => 4)
 const KIND_NN = Dict(1 => 1, 2 => 2, 3 => 2, 4 => 1, 5 => 1, 6 => 1)
 
@@ -208,6 +211,7 @@ mutable struct BatchRunner
     progress::Base.RefValue{Any}      # the ProgressMeter.Progress of the run in flight (showprogress = true)
     showprogress::Bool
     meas::Any                         # the armed MeasureSpec (nothing: none)
+    sources::Set{Int}                 # the input rows (1-based) that have a source
 end
 
 # @showprogress of run!(runner, y, u) (src/ACME.jl:587-604,653): the library reports after every time slice of a
@@ -226,7 +230,7 @@ function BatchRunner(model::DiscreteModel, n::Integer; device::Integer=-1,
     b = Ref{Ptr{Cvoid}}()
     check(ccall((:acme_batch_create, lib), Cint, (Ptr{Cvoid}, Clonglong, Ref{AcmeOptions}, Ref{Ptr{Cvoid}}),
                 mh.h, n, opts, b))
-    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress, nothing)
+    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress, nothing, Set{Int}())
     finalizer(r -> ccall((:acme_batch_destroy, lib), Cvoid, (Ptr{Cvoid},), r.h), r)
     if showprogress
         cb = @cfunction(progress_trampoline, Cvoid, (Ptr{Cvoid}, Clonglong, Clonglong))
@@ -513,6 +517,112 @@ function measure!(r::BatchRunner, u::Array{Float64,3})
     return r
 end
 
+# ---- sources: input rows generated on the device -----------------------------------------------------------------
+# a per-instance parameter as the ABI takes it: nothing -> NULL (the default for every instance), a number -> N copies
+perinstance(::Type{T}, ::Nothing, n) where {T} = T[]
+perinstance(::Type{T}, v::Number, n) where {T} = fill(T(v), n)
+function perinstance(::Type{T}, v::AbstractVector, n) where {T}
+    length(v) == n || throw(DimensionMismatch("per-instance source parameters need $n values"))
+    return convert(Vector{T}, v)
+end
+ptr_or_null(v::Vector{T}) where {T} = isempty(v) ? Ptr{T}(C_NULL) : pointer(v)
+
+"""
+    set_source!(runner, row, :const; offset=nothing)
+    set_source!(runner, row, :sine; f_den, f_num=nothing, phase=nothing, amp=nothing, offset=nothing)
+    set_source!(runner, row, :table; table, amp=nothing, offset=nothing)
+
+Give input row `row` (1-based) a source (`acme_batch_set_source_*`): the library generates the row on the device -- at
+source clock n (base-rate samples since the first source was armed) instance i gets `offset[i]`,
+`fma(amp[i], sin(2π κ / f_den), offset[i])` with κ = (f_num[i] n + phase[i]) mod f_den reduced exactly in integers, or
+`fma(amp[i], table[n mod P + 1], offset[i])`.  Parameters: `nothing` (amp 1, the others 0), a number, or N values.
+`run_sources!` then runs without these rows; its results are those of `run!` on `render_sources`' array, bit for bit.
+"""
+function set_source!(r::BatchRunner, row::Integer, kind::Symbol; f_den::Integer=0, f_num=nothing, phase=nothing,
+                     table=nothing, amp=nothing, offset=nothing)
+    a, o = perinstance(Cdouble, amp, r.n), perinstance(Cdouble, offset, r.n)
+    if kind === :const
+        GC.@preserve o check(ccall((:acme_batch_set_source_const, lib), Cint, (Ptr{Cvoid}, Cint, Ptr{Cdouble}), r.h, row - 1, ptr_or_null(o)))
+    elseif kind === :sine
+        f, p = perinstance(Clonglong, f_num, r.n), perinstance(Clonglong, phase, r.n)
+        GC.@preserve f p a o check(ccall((:acme_batch_set_source_sine, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Clonglong, Ptr{Clonglong}, Ptr{Clonglong}, Ptr{Cdouble}, Ptr{Cdouble}),
+                    r.h, row - 1, f_den, ptr_or_null(f), ptr_or_null(p), ptr_or_null(a), ptr_or_null(o)))
+    elseif kind === :table
+        table === nothing && error("a table source needs a table")
+        w = convert(Vector{Cdouble}, table)
+        GC.@preserve w a o check(ccall((:acme_batch_set_source_table, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Clonglong, Ptr{Cdouble}, Ptr{Cdouble}),
+                    r.h, row - 1, w, length(w), ptr_or_null(a), ptr_or_null(o)))
+    else
+        error("unknown source kind $kind: :const, :sine or :table")
+    end
+    push!(r.sources, Int(row))
+    return r
+end
+
+"the row (1-based) is the caller's again (`acme_batch_clear_source`); `row = 0`: every row"
+function clear_source!(r::BatchRunner, row::Integer=0)
+    check(ccall((:acme_batch_clear_source, lib), Cint, (Ptr{Cvoid}, Cint), r.h, row - 1))
+    row == 0 ? empty!(r.sources) : delete!(r.sources, Int(row))
+    return r
+end
+
+"the source clock: base-rate samples the source runs have advanced since the first source was armed"
+function source_clock(r::BatchRunner)
+    n = Ref{Clonglong}(0)
+    check(ccall((:acme_batch_get_source_clock, lib), Cint, (Ptr{Cvoid}, Ref{Clonglong}), r.h, n))
+    return Int(n[])
+end
+source_clock!(r::BatchRunner, n::Integer) = (check(ccall((:acme_batch_set_source_clock, lib), Cint, (Ptr{Cvoid}, Clonglong), r.h, n)); r)
+
+# the rows without a source: nu_var × T × N, or nothing when every row has one
+function checkuvar(r::BatchRunner, u_var, T::Integer)
+    nuv = ACME.nu(r.model) - length(r.sources)
+    isempty(r.sources) && error("no input row has a source (set_source!)")
+    if u_var === nothing
+        nuv == 0 || throw(DimensionMismatch("u_var must be $nuv × T × $(r.n)"))
+        return Ptr{Cdouble}(C_NULL), Int(T)
+    end
+    size(u_var, 1) == nuv && size(u_var, 3) == r.n || throw(DimensionMismatch("u_var must be $nuv × T × $(r.n)"))
+    return pointer(u_var), size(u_var, 2)
+end
+
+"""
+    run_sources!(runner, y, T; u_var=nothing)
+    run_sources!(runner, T; u_var=nothing)        # measured run: no outputs
+
+`run!` with the sourced rows generated on the device (`acme_batch_run_sources`): `u_var` (nu_var × T × N) holds only the
+rows without a source, in row order; `nothing` when every row has one.  Without `y` (a measurement armed) nothing of the
+outputs is stored: a level sweep owns no N × T array anywhere.
+"""
+function run_sources!(r::BatchRunner, y::Union{Array{Float64,3},Nothing}, T::Integer; u_var::Union{Array{Float64,3},Nothing}=nothing)
+    up, T = checkuvar(r, u_var, T)
+    y === nothing || size(y) == (ACME.ny(r.model), T, r.n) || throw(DimensionMismatch("output must be $(ACME.ny(r.model)) × $T × $(r.n)"))
+    y === nothing && r.meas === nothing && error("run_sources! without y needs an armed measurement (set_measurement!)")
+    GC.@preserve r u_var y check(ccall((:acme_batch_run_sources, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Clonglong, Cint, Ptr{Cvoid}),
+                r.h, up, y === nothing ? Ptr{Cdouble}(C_NULL) : pointer(y), T, ACME_MEM_HOST, C_NULL))
+    checkreports!(r)
+    return y === nothing ? r : y
+end
+run_sources!(r::BatchRunner, T::Integer; kwargs...) = run_sources!(r, nothing, T; kwargs...)
+
+"""
+    render_sources(runner, T; u_var=nothing) -> nu × T × N
+
+The input a source run of `T` samples would feed from the current clock (`acme_batch_render_sources`): sourced rows
+generated, the others from `u_var` (zeros if `nothing`).  Advances neither the clock nor the model.
+"""
+function render_sources(r::BatchRunner, T::Integer; u_var::Union{Array{Float64,3},Nothing}=nothing)
+    up = u_var === nothing ? Ptr{Cdouble}(C_NULL) : checkuvar(r, u_var, T)[1]
+    u = Array{Float64,3}(undef, ACME.nu(r.model), T, r.n)
+    GC.@preserve u_var check(ccall((:acme_batch_render_sources, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Clonglong, Cint, Ptr{Cvoid}),
+                r.h, up, u, T, ACME_MEM_HOST, C_NULL))
+    return u
+end
+
 # ---- MultiBatchRunner: N instances over the GPUs of one node, one Julia process -----------------------
 "contiguous instance range (1-based) of part `k` of `parts`; sizes differ by at most one (acme_jl_amd/dist.py)"
 function shard_range(n::Integer, k::Integer, parts::Integer)
@@ -576,6 +686,45 @@ function run!(mr::MultiBatchRunner, u::Array{Float64,3})
     y = Array{Float64,3}(undef, ACME.ny(mr.model), size(u, 2), mr.n)
     run!(mr, y, u)
     return y
+end
+
+# sources on every device's batch, each with its instances' parameters
+slicepar(v, rg) = v isa AbstractVector ? v[rg] : v
+function set_source!(mr::MultiBatchRunner, row::Integer, kind::Symbol; f_den::Integer=0, f_num=nothing, phase=nothing,
+                     table=nothing, amp=nothing, offset=nothing)
+    for (r, rg) in zip(mr.runners, mr.ranges)
+        set_source!(r, row, kind; f_den=f_den, f_num=slicepar(f_num, rg), phase=slicepar(phase, rg), table=table,
+                    amp=slicepar(amp, rg), offset=slicepar(offset, rg))
+    end
+    return mr
+end
+clear_source!(mr::MultiBatchRunner, row::Integer=0) = (foreach(r -> clear_source!(r, row), mr.runners); mr)
+
+"`run_sources!` on every device at once (`acme_batch_run_sources_async`, then joined); every row has a source"
+function run_sources!(mr::MultiBatchRunner, y::Union{Array{Float64,3},Nothing}, T::Integer)
+    sy = ACME.ny(mr.model) * T
+    y === nothing || size(y) == (ACME.ny(mr.model), T, mr.n) || throw(DimensionMismatch("output must be $(ACME.ny(mr.model)) × $T × $(mr.n)"))
+    GC.@preserve y begin
+        started = 0
+        rcs, msg = Cint[], ""
+        try
+            for (r, rg) in zip(mr.runners, mr.ranges)
+                check(ccall((:acme_batch_run_sources_async, lib), Cint,
+                            (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Clonglong, Cint, Ptr{Cvoid}),
+                            r.h, Ptr{Cdouble}(C_NULL), y === nothing ? Ptr{Cdouble}(C_NULL) : pointer(y) + 8 * sy * (first(rg) - 1),
+                            T, ACME_MEM_HOST, C_NULL))
+                started += 1
+            end
+        finally
+            rcs = [ccall((:acme_batch_wait, lib), Cint, (Ptr{Cvoid},), r.h) for r in mr.runners[1:started]]
+            msg = lasterror()
+        end
+        all(rc -> rc >= 0, rcs) || error("libacme_hip: " * msg)
+    end
+    for (r, rg) in zip(mr.runners, mr.ranges)
+        checkreports!(r, first(rg) - 1)
+    end
+    return y === nothing ? mr : y
 end
 
 reports(mr::MultiBatchRunner) = reduce(vcat, [reports(r) for r in mr.runners])
