@@ -148,6 +148,14 @@ struct acme_batch {
         double *d_tw = nullptr;                  // one chunk's twiddles, [H][MEAS_CHUNK] pairs
         double *d_ys = nullptr;                  // y = NULL: one slice of base-rate outputs, [N][TS][ny]
         size_t cap_ys = 0;
+        // per-instance fundamentals (acme_batch_set_measurement_per_instance): the plan of acme_measure.h, built at arming
+        bool pi = false;
+        int F = 0;                               // distinct f_num: groups, rows of the table [F][H][chunk]
+        long long chunk = MEAS_CHUNK;            // samples per step (the table's budget)
+        std::vector<long long> perm;             // the plan on the host (acme_batch_get_measurement_plan)
+        std::vector<int> wgrp;
+        long long *d_fnum_g = nullptr, *d_perm = nullptr;       // [F], [N nrows]
+        int *d_sgrp = nullptr, *d_wgrp = nullptr;               // [N nrows], [(N nrows + 63) / 64]
     } meas;
     // Input rows generated on the device (acme_batch_set_source_*, acme_source.h): the rows' descriptions and per-instance
     // parameters in device memory, the source clock
@@ -725,6 +733,12 @@ int acme_batch_release_host_buffers(acme_batch *b) {
     return ACME_OK;
 }
 
+static void meas_release(acme_batch::Measurement &M) {
+    (void)be::dfree(M.d_acc); (void)be::dfree(M.d_tw); (void)be::dfree(M.d_ys);
+    (void)be::dfree(M.d_fnum_g); (void)be::dfree(M.d_perm); (void)be::dfree(M.d_sgrp); (void)be::dfree(M.d_wgrp);
+    M = acme_batch::Measurement{};
+}
+
 void acme_batch_destroy(acme_batch *b) {
     if (!b) return;
     join_worker(b);
@@ -744,7 +758,7 @@ void acme_batch_destroy(acme_batch *b) {
     (void)be::flag_free(b->h_u_ready);
     (void)be::dfree(b->os.d_taps); (void)be::dfree(b->os.d_hist_u); (void)be::dfree(b->os.d_hist_y);
     (void)be::dfree(b->os.d_ou); (void)be::dfree(b->os.d_oy); (void)be::dfree(b->os.d_base);
-    (void)be::dfree(b->meas.d_acc); (void)be::dfree(b->meas.d_tw); (void)be::dfree(b->meas.d_ys);
+    meas_release(b->meas);
     src_release(b, -1);
     (void)be::dfree(b->src.d_rows); (void)be::dfree(b->src.d_ys);
     for (auto &e : b->os.ev) if (e) (void)be::event_destroy(e);
@@ -1275,11 +1289,16 @@ static int meas_step(acme_batch *b, const double *y, long long n, long long pitc
     acme_batch::Measurement &M = b->meas;
     const long long end = M.length ? M.start + M.length : LLONG_MAX;
     const long long lo = M.pos > M.start ? M.pos : M.start, hi = M.pos + n < end ? M.pos + n : end;
-    for (long long s = lo; M.nrows > 0 && s < hi; s += MEAS_CHUNK) {
-        const long long len = hi - s < MEAS_CHUNK ? hi - s : MEAS_CHUNK;
-        const MeasTwArgs W{M.d_tw, s - M.start, len, M.f_num, M.f_den, M.H};
+    for (long long s = lo; M.nrows > 0 && s < hi; s += M.chunk) {
+        const long long len = hi - s < M.chunk ? hi - s : M.chunk;
         MeasArgs A{y, M.d_acc, M.d_tw, b->N, len, pitch, s - M.pos, b->P.actual.ny, M.nrows, M.H, {}};
         memcpy(A.row, M.row, sizeof(A.row));
+        if (M.pi) {
+            const MeasPiTwArgs W{M.d_tw, M.d_fnum_g, s - M.start, len, M.f_den, M.H, M.F};
+            HIPCHK(meas_pi_launch(W, MeasPiArgs{A, M.d_perm, M.d_sgrp, M.d_wgrp}, st));
+            continue;
+        }
+        const MeasTwArgs W{M.d_tw, s - M.start, len, M.f_num, M.f_den, M.H};
         HIPCHK(meas_launch(W, A, st));
     }
     M.pos += n;
@@ -2075,8 +2094,39 @@ static int meas_zero(acme_batch *b) {
     return ACME_OK;
 }
 
+// per-instance fundamentals: the instances grouped by distinct f_num, the plan (acme_measure.h) to the device.  The table's
+// budget is MEAS_PI_BUDGET; ACME_MEAS_TABLE_BUDGET (bytes) in the environment overrides it (tests: chunks of one tile)
+static int meas_pi_arm(acme_batch *b, const long long *f_num) {
+    acme_batch::Measurement &M = b->meas;
+    const size_t N = (size_t)b->N;
+    std::vector<long long> fg(f_num, f_num + N);
+    std::sort(fg.begin(), fg.end());
+    fg.erase(std::unique(fg.begin(), fg.end()), fg.end());
+    std::vector<int> grp(N), sgrp;
+    for (size_t i = 0; i < N; ++i) grp[i] = (int)(std::lower_bound(fg.begin(), fg.end(), f_num[i]) - fg.begin());
+    M.pi = true;
+    M.F = (int)fg.size();
+    M.f_num = fg.empty() ? 0 : fg[0];
+    long long budget = MEAS_PI_BUDGET;
+    if (const char *e = getenv("ACME_MEAS_TABLE_BUDGET")) { const long long v = atoll(e); if (v >= 1) budget = v; }
+    M.chunk = meas_pi_chunk(M.F > 0 ? M.F : 1, M.H, budget);
+    meas_pi_plan(grp, b->N, M.nrows, M.F, &M.perm, &sgrp, &M.wgrp);
+    auto put = [](auto **d, const auto &v) -> int {
+        if (v.empty()) return ACME_OK;
+        HIPCHK(be::dmalloc((void **)d, sizeof(v[0]) * v.size()));
+        HIPCHK(be::copy_h2d(*d, v.data(), sizeof(v[0]) * v.size()));
+        return ACME_OK;
+    };
+    int rc = put(&M.d_fnum_g, fg);
+    if (rc == ACME_OK) rc = put(&M.d_perm, M.perm);
+    if (rc == ACME_OK) rc = put(&M.d_sgrp, sgrp);
+    if (rc == ACME_OK) rc = put(&M.d_wgrp, M.wgrp);
+    return rc;
+}
+
 // spec = nullptr: off
-struct MeasSpec { long long start, length, f_num, f_den; int harmonics; unsigned long long rows; };
+// f_num_i != nullptr: per-instance fundamentals, host [N]
+struct MeasSpec { long long start, length, f_num, f_den; int harmonics; unsigned long long rows; const long long *f_num_i; };
 static int set_measurement(acme_batch *b, const MeasSpec *spec) {
     join_worker(b);
     if (!b) return fail(ACME_ERR_INVALID, "null batch");
@@ -2093,14 +2143,16 @@ static int set_measurement(acme_batch *b, const MeasSpec *spec) {
         const unsigned long long rows = spec->rows ? spec->rows : ny >= 64 ? ~0ull : ((1ull << ny) - 1ull);
         for (int r = 0; r < 64 && r < ny; ++r)
             if (rows >> r & 1ull) row[nrows++] = (unsigned char)r;
+        for (long long i = 0; spec->f_num_i && i < b->N; ++i)
+            if (spec->f_num_i[i] < 0 || spec->f_num_i[i] >= spec->f_den)
+                return fail(ACME_ERR_INVALID, "measurement: f_num of instance " + std::to_string(i) + " is outside 0 ... f_den - 1");
         if (b->iso_thr > 0.0)
             return fail(ACME_ERR_UNSUPPORTED, "measurements are not available while the isolation of slow instances is in force");
     }
     ON_DEVICE(b);
     HIPCHK(be::device_sync());          // (a launch still in flight may write the accumulators)
     acme_batch::Measurement &M = b->meas;
-    (void)be::dfree(M.d_acc); (void)be::dfree(M.d_tw); (void)be::dfree(M.d_ys);
-    M = acme_batch::Measurement{};
+    meas_release(M);
     if (!spec) return ACME_OK;
     M.start = spec->start;
     M.length = spec->length;
@@ -2111,7 +2163,11 @@ static int set_measurement(acme_batch *b, const MeasSpec *spec) {
     M.nrows = nrows;
     memcpy(M.row, row, sizeof(row));
     HIPCHK(be::dmalloc((void **)&M.d_acc, sizeof(double) * (size_t)(4 + 2 * M.H) * (size_t)b->N * nrows));
-    HIPCHK(be::dmalloc((void **)&M.d_tw, sizeof(double) * 2 * (size_t)M.H * MEAS_CHUNK));
+    if (spec->f_num_i) {
+        const int rc = meas_pi_arm(b, spec->f_num_i);
+        if (rc != ACME_OK) { meas_release(M); return rc; }
+    }
+    HIPCHK(be::dmalloc((void **)&M.d_tw, sizeof(double) * 2 * (size_t)(M.pi ? M.F : 1) * (size_t)M.H * (size_t)M.chunk));
     for (auto &e : b->os.ev) if (!e) HIPCHK(be::event_create(&e));      // (the host pipeline of run_os)
     const int rc = meas_zero(b);
     if (rc != ACME_OK) return rc;
@@ -2121,8 +2177,27 @@ static int set_measurement(acme_batch *b, const MeasSpec *spec) {
 
 int acme_batch_set_measurement(acme_batch *b, long long start, long long length, long long f_num, long long f_den,
                                int harmonics, unsigned long long rows) {
-    const MeasSpec spec{start, length, f_num, f_den, harmonics, rows};
+    const MeasSpec spec{start, length, f_num, f_den, harmonics, rows, nullptr};
     return set_measurement(b, &spec);
+}
+
+int acme_batch_set_measurement_per_instance(acme_batch *b, long long start, long long length, long long f_den,
+                                            long long *f_num, int harmonics, unsigned long long rows) {
+    if (b && !f_num) return fail(ACME_ERR_INVALID, "measurement: null f_num");
+    const MeasSpec spec{start, length, 0, f_den, harmonics, rows, f_num};
+    return set_measurement(b, &spec);
+}
+
+int acme_batch_get_measurement_plan(acme_batch *b, long long *n_groups, long long *chunk, long long *perm, int *wave_group) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const acme_batch::Measurement &M = b->meas;
+    if (!M.on || !M.pi) return fail(ACME_ERR_INVALID, "no per-instance measurement is armed");
+    if (n_groups) *n_groups = M.F;
+    if (chunk) *chunk = M.chunk;
+    if (perm && !M.perm.empty()) memcpy(perm, M.perm.data(), sizeof(long long) * M.perm.size());
+    if (wave_group && !M.wgrp.empty()) memcpy(wave_group, M.wgrp.data(), sizeof(int) * M.wgrp.size());
+    return ACME_OK;
 }
 
 int acme_batch_clear_measurement(acme_batch *b) { return set_measurement(b, nullptr); }

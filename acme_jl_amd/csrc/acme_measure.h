@@ -19,11 +19,26 @@
 // loads along the samples (contiguous per pair), and every wave then reads its lane's column.  A harmonic wave holds
 // 64 samples' twiddles in its lanes and broadcasts the current one (v_readlane: no memory access).
 //
+// PER-INSTANCE FUNDAMENTALS (acme_batch_set_measurement_per_instance): instance i correlates with f_num[i] / f_den.  The
+// instances are grouped by distinct f_num on the host at arming (meas_pi_plan): F groups, one table row [H][len] each, written
+// by a twiddle kernel with a group index (meas_pi_tw: the same meas_twiddle per element).  The table is bounded:
+// MEAS_PI_BUDGET = 64 MiB; the chunk length is the largest multiple of MEAS_TILE <= MEAS_CHUNK with F H len 16 B inside the
+// budget, and one tile at least (every twiddle is a closed form of the sample's number and every accumulator one chain, so
+// the chunk length cannot change a result).  Pairs go to lanes through a permutation sorted by group, and the rule between
+// the two inner loops is:
+//   a group's pairs fill whole waves (64 lanes) first, in group order; the remainders of all groups, again in group order,
+//   share the waves behind them without padding.  A wave whose pairs share ONE group is UNIFORM and runs the broadcast
+//   loop above on its group's table row; any other wave is MIXED: each lane reads its own group's (cos, sin) pairs with
+//   16-byte loads, eight samples at a time ahead of the fma chain.
+// Unit 0 (the moments) does not read the table: the same chain, the same bits.  F = 1 is the shared layout with one more
+// indirection; F = N is mixed waves throughout with no idle lanes.
+//
 // The per-element functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with g++).
 #pragma once
 #include <climits>
 #include <cmath>
+#include <vector>
 
 #include "acme_common.h"
 
@@ -49,6 +64,23 @@ struct MeasTwArgs {
     int H;
 };
 
+// per-instance fundamentals: the plan's device arrays beside the shared arguments (A.tw: [F][H][len] pairs)
+struct MeasPiArgs {
+    MeasArgs A;
+    const long long *perm;      // [P]: slot -> pair, sorted by group as the rule above says
+    const int *sgrp;            // [P]: slot -> group of its pair's instance
+    const int *wgrp;            // [(P + 63) / 64]: wave -> its one group, or -1 (mixed)
+};
+
+struct MeasPiTwArgs {
+    double *tw;                 // [F][H][len] pairs (cos, sin) of samples m0 ... m0 + len - 1 (window-relative)
+    const long long *fnum_g;    // [F]: the groups' f_num, 0 <= f_num < f_den
+    long long m0, len, f_den;
+    int H, F;
+};
+
+constexpr long long MEAS_PI_BUDGET = 64ll << 20;    // bytes of twiddle table a chunk may take (one tile is always allowed)
+
 // cos / sin of 2 pi ((h f_num m) mod f_den) / f_den, the phase reduced exactly (h <= 32, f_den < 2^31: products < 2^62)
 // and taken to (-pi, pi] before the one rounding of the angle
 // the angle 2 pi k / f_den of a reduced phase 0 <= k < f_den < 2^31, taken to (-pi, pi] first: two roundings, the quotient's
@@ -69,6 +101,12 @@ ACME_HD inline void meas_twiddle(long long h, long long m, long long f_num, long
 ACME_HD inline void meas_tw(const MeasTwArgs &A, long long idx) {
     const long long h = idx / A.len, t = idx - h * A.len;
     meas_twiddle(h + 1, A.m0 + t, A.f_num, A.f_den, &A.tw[2 * idx], &A.tw[2 * idx + 1]);
+}
+
+ACME_HD inline void meas_pi_tw(const MeasPiTwArgs &A, long long idx) {
+    const long long per = A.H * A.len, g = idx / per, r = idx - g * per;
+    const long long h = r / A.len, t = r - h * A.len;
+    meas_twiddle(h + 1, A.m0 + t, A.fnum_g[g], A.f_den, &A.tw[2 * idx], &A.tw[2 * idx + 1]);
 }
 
 // NaN sticks: once an accumulator is NaN it stays so
@@ -112,6 +150,46 @@ inline void meas_shape(int H, int *waves, int *groups) {
     const int U = H + 1;
     *groups = (U + MEAS_MAX_WAVES - 1) / MEAS_MAX_WAVES;
     *waves = (U + *groups - 1) / *groups;
+}
+
+// samples per step of a per-instance measurement: F groups, H harmonics, `budget` bytes of table
+inline long long meas_pi_chunk(long long F, int H, long long budget) {
+    if (H == 0) return MEAS_CHUNK;
+    long long len = budget / (F * H * 16) / MEAS_TILE * MEAS_TILE;
+    if (len > MEAS_CHUNK) len = MEAS_CHUNK;
+    return len < MEAS_TILE ? MEAS_TILE : len;
+}
+
+// the plan of a per-instance measurement from the instances' groups grp[n] (0 ... F - 1): perm, sgrp, wgrp as MeasPiArgs
+// describes them.  Whole waves of one group first, the remainders packed behind them, both in group order and, inside a
+// group, in pair order.
+template <class VL, class VI>
+inline void meas_pi_plan(const VI &grp, long long n, int nrows, int F, VL *perm, VI *sgrp, VI *wgrp) {
+    const long long P = n * nrows;
+    std::vector<long long> cnt((size_t)F, 0), at((size_t)F + 1, 0);
+    for (long long i = 0; i < n; ++i) cnt[(size_t)grp[(size_t)i]] += nrows;
+    // slots of the whole waves, then of the remainders
+    std::vector<long long> full((size_t)F), rest((size_t)F);
+    long long s = 0;
+    for (int g = 0; g < F; ++g) { full[(size_t)g] = s; s += cnt[(size_t)g] / 64 * 64; }
+    for (int g = 0; g < F; ++g) { rest[(size_t)g] = s; s += cnt[(size_t)g] % 64; }
+    perm->assign((size_t)P, 0);
+    sgrp->assign((size_t)P, 0);
+    std::vector<long long> seen((size_t)F, 0);
+    for (long long p = 0; p < P; ++p) {
+        const int g = grp[(size_t)(p / nrows)];
+        const long long k = seen[(size_t)g]++, whole = cnt[(size_t)g] / 64 * 64;
+        const long long slot = k < whole ? full[(size_t)g] + k : rest[(size_t)g] + (k - whole);
+        (*perm)[(size_t)slot] = p;
+        (*sgrp)[(size_t)slot] = g;
+    }
+    wgrp->assign((size_t)((P + 63) / 64), 0);
+    for (long long w = 0; w * 64 < P; ++w) {
+        int g = (*sgrp)[(size_t)(w * 64)];
+        for (long long q = w * 64; q < P && q < w * 64 + 64; ++q)
+            if ((*sgrp)[(size_t)q] != g) g = -1;
+        (*wgrp)[(size_t)w] = g;
+    }
 }
 
 }  // namespace acme
@@ -195,6 +273,107 @@ __global__ __launch_bounds__(1024) void acme_meas_kernel(acme::MeasArgs A) {
         if (u == 0) { A.acc[2 * P + p] = a2; A.acc[3 * P + p] = a3; }
     }
 }
+__global__ __launch_bounds__(256) void acme_meas_pi_tw_kernel(acme::MeasPiTwArgs A) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx < (long long)A.F * A.H * A.len) acme::meas_pi_tw(A, idx);
+}
+
+// per-instance fundamentals: acme_meas_kernel with the pairs taken through the plan's permutation; a uniform wave reads its
+// group's table row and broadcasts, a mixed wave's lanes read their own rows (16-byte loads, eight samples ahead)
+__global__ __launch_bounds__(1024) void acme_meas_pi_kernel(acme::MeasPiArgs B) {
+    using namespace acme;
+    const MeasArgs &A = B.A;
+    __shared__ double tile[64][MEAS_TILE + 1];          // [slot][sample]: column reads by lane hit distinct banks
+    __shared__ long long base[64];                      // a slot's pair: its first element of the chunk in y
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const long long P = A.n * A.nrows, p0 = (long long)blockIdx.x * 64;
+    const int u = blockIdx.y * nw + w;
+    const bool mine = u <= A.H && p0 + lane < P;
+    const long long p = p0 + lane < P ? B.perm[p0 + lane] : 0;
+    if (threadIdx.x < 64 && p0 + lane < P) {
+        const long long i = p / A.nrows;
+        base[lane] = (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    }
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    const int ia = u == 0 ? 0 : 2 + 2 * u;
+    if (mine) {
+        a0 = A.acc[ia * P + p];
+        a1 = A.acc[(ia + 1) * P + p];
+        if (u == 0) { a2 = A.acc[2 * P + p]; a3 = A.acc[3 * P + p]; }
+    }
+    const int wg = B.wgrp[blockIdx.x];                 // (wave-uniform: one value per block)
+    const int g = wg >= 0 ? wg : mine ? B.sgrp[p0 + lane] : 0;
+    const double *tw = A.tw + 2 * ((long long)g * A.H + (u > 0 ? u - 1 : 0)) * A.len;
+    for (long long tb = 0; tb < A.len; tb += MEAS_TILE) {
+        const int nt = (int)(A.len - tb < MEAS_TILE ? A.len - tb : MEAS_TILE);
+        __syncthreads();                                // (the previous tile has been read by every wave)
+        for (int pp = w; pp < 64; pp += nw)
+            if (p0 + pp < P && lane < nt) tile[pp][lane] = A.y[base[pp] + (tb + lane) * A.ny];
+        __syncthreads();
+        if (u > A.H) continue;
+        if (u == 0) {
+            for (int t = 0; t < nt; ++t) {
+                const double v = tile[lane][t];
+                a0 += v;
+                a1 = fma(v, v, a1);
+                a2 = meas_min(a2, v);
+                a3 = meas_max(a3, v);
+            }
+        } else if (wg >= 0) {
+            double cl = 0.0, sl = 0.0;                 // lane t holds sample tb + t's twiddle
+            if (lane < nt) { cl = tw[2 * (tb + lane)]; sl = tw[2 * (tb + lane) + 1]; }
+            if (nt == MEAS_TILE) {
+#pragma unroll 8
+                for (int t = 0; t < MEAS_TILE; ++t) {
+                    const double v = tile[lane][t];
+                    a0 = fma(v, acme_meas_bcast(cl, t), a0);
+                    a1 = fma(v, acme_meas_bcast(sl, t), a1);
+                }
+            } else {
+                for (int t = 0; t < nt; ++t) {
+                    const double v = tile[lane][t];
+                    a0 = fma(v, acme_meas_bcast(cl, t), a0);
+                    a1 = fma(v, acme_meas_bcast(sl, t), a1);
+                }
+            }
+        } else if (mine) {
+            const double2 *tl = reinterpret_cast<const double2 *>(tw) + tb;    // (16-byte aligned: pairs of a hipMalloc'ed table)
+            if (nt == MEAS_TILE) {
+                double2 nx[8];
+#pragma unroll
+                for (int k = 0; k < 8; ++k) nx[k] = tl[k];
+#pragma unroll
+                for (int t = 0; t < MEAS_TILE; t += 8) {
+                    double2 cs[8];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) cs[k] = nx[k];
+                    if (t + 8 < MEAS_TILE) {           // the next eight samples' loads are in flight under this chain
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) nx[k] = tl[t + 8 + k];
+                    }
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        const double v = tile[lane][t + k];
+                        a0 = fma(v, cs[k].x, a0);
+                        a1 = fma(v, cs[k].y, a1);
+                    }
+                }
+            } else {
+                for (int t = 0; t < nt; ++t) {
+                    const double2 cs = tl[t];
+                    const double v = tile[lane][t];
+                    a0 = fma(v, cs.x, a0);
+                    a1 = fma(v, cs.y, a1);
+                }
+            }
+        }
+    }
+    if (mine) {
+        A.acc[ia * P + p] = a0;
+        A.acc[(ia + 1) * P + p] = a1;
+        if (u == 0) { A.acc[2 * P + p] = a2; A.acc[3 * P + p] = a3; }
+    }
+}
 namespace acme {
 inline int meas_launch(const MeasTwArgs &T, const MeasArgs &A, hipStream_t st) {
     if (A.H > 0) {
@@ -208,6 +387,20 @@ inline int meas_launch(const MeasTwArgs &T, const MeasArgs &A, hipStream_t st) {
     hipLaunchKernelGGL(acme_meas_kernel, dim3((unsigned)((P + 63) / 64), (unsigned)groups), dim3(64 * waves), 0, st, A);
     return (int)hipGetLastError();
 }
+inline int meas_pi_launch(const MeasPiTwArgs &T, const MeasPiArgs &B, hipStream_t st) {
+    const MeasArgs &A = B.A;
+    if (A.H > 0) {
+        const long long total = (long long)T.F * A.H * A.len;
+        hipLaunchKernelGGL(acme_meas_pi_tw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, T);
+        const int e = (int)hipGetLastError();
+        if (e) return e;
+    }
+    int waves = 1, groups = 1;
+    meas_shape(A.H, &waves, &groups);
+    const long long P = A.n * A.nrows;
+    hipLaunchKernelGGL(acme_meas_pi_kernel, dim3((unsigned)((P + 63) / 64), (unsigned)groups), dim3(64 * waves), 0, st, B);
+    return (int)hipGetLastError();
+}
 }  // namespace acme
 #else
 namespace acme {
@@ -215,6 +408,16 @@ inline int meas_launch(const MeasTwArgs &T, const MeasArgs &A, void *) {
     for (long long idx = 0; idx < A.H * A.len; ++idx) meas_tw(T, idx);
     for (long long p = 0; p < A.n * A.nrows; ++p)
         for (int u = 0; u <= A.H; ++u) meas_chain(A, p, u);
+    return 0;
+}
+// slot by slot through the plan, every unit's chain on the table row of the slot's group
+inline int meas_pi_launch(const MeasPiTwArgs &T, const MeasPiArgs &B, void *) {
+    for (long long idx = 0; idx < (long long)T.F * B.A.H * B.A.len; ++idx) meas_pi_tw(T, idx);
+    for (long long q = 0; q < B.A.n * B.A.nrows; ++q) {
+        MeasArgs A = B.A;
+        A.tw = B.A.tw + 2 * (long long)B.sgrp[q] * A.H * A.len;
+        for (int u = 0; u <= A.H; ++u) meas_chain(A, B.perm[q], u);
+    }
     return 0;
 }
 }  // namespace acme

@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "acme_batch_set_resabstol", "acme_batch_get_state", "acme_batch_set_state",
     "acme_oversampling_design", "acme_batch_set_oversampling",
     "acme_batch_set_measurement", "acme_batch_clear_measurement", "acme_batch_reset_measurement", "acme_batch_get_measurement",
+    "acme_batch_set_measurement_per_instance", "acme_batch_get_measurement_plan",
     "acme_batch_set_source_const", "acme_batch_set_source_sine", "acme_batch_set_source_table", "acme_batch_clear_source",
     "acme_batch_set_source_clock", "acme_batch_get_source_clock", "acme_batch_run_sources", "acme_batch_run_sources_async",
     "acme_batch_render_sources",
@@ -147,6 +148,10 @@ class Library:
         L.acme_oversampling_design.argtypes = [C.c_int, dp, C.c_int]
         L.acme_batch_set_oversampling.argtypes = [vp, C.c_int, dp, C.c_int, dp, C.c_int, C.c_ulonglong]
         L.acme_batch_set_measurement.argtypes = [vp, C.c_longlong, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, C.c_ulonglong]
+        L.acme_batch_set_measurement_per_instance.argtypes = [vp, C.c_longlong, C.c_longlong, C.c_longlong, C.POINTER(C.c_longlong),
+                                                              C.c_int, C.c_ulonglong]
+        L.acme_batch_get_measurement_plan.argtypes = [vp, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong),
+                                                      C.POINTER(C.c_int)]
         L.acme_batch_clear_measurement.argtypes = [vp]
         L.acme_batch_reset_measurement.argtypes = [vp]
         L.acme_batch_get_measurement.argtypes = [vp, dp, C.POINTER(C.c_longlong)]
@@ -343,6 +348,7 @@ class ModelRunner:
         self._os = (1, 1, 1)            # oversampling: factor, interpolation taps, decimation taps
         self._meas = None               # measurement: (harmonics, measured rows) while armed
         self._sources = {}              # input row -> kind, while the row has a source
+        self._sine = {}                 # input row -> (f_den, f_num as armed) of its sine source
         self._progress_cb = None
         if showprogress:
             fn = showprogress if callable(showprogress) else _print_progress
@@ -400,15 +406,50 @@ class ModelRunner:
         return int(d) if d == int(d) else d
 
     # ---- output measurements ------------------------------------------------------------------
-    def set_measurement(self, start=0, length=0, f0=None, harmonics=0, rows=None):
+    def set_measurement(self, start=0, length=0, f0=None, harmonics=0, rows=None, f_den=None, f_num=None, f0_from_source=None):
         """Arm an output measurement (``acme_batch_set_measurement``): from now on every run feeds per instance and output
         row (``rows``: which, None = all) the mean, RMS, min, max and the complex amplitudes of ``harmonics`` harmonics of
         the fundamental ``f0`` -- a ``Fraction`` of fs or ``(num, den)`` -- over the samples ``start <= n < start + length``
-        counted from now (``length=0``: all from ``start`` on).  ``measure`` then runs without storing y at all."""
-        spec, rows = measure_spec(self.model.ny, start, length, f0, harmonics, rows)
-        self.lib.check(self.lib.L.acme_batch_set_measurement(self.h, *spec))
+        counted from now (``length=0``: all from ``start`` on).  ``measure`` then runs without storing y at all.
+
+        A fundamental PER INSTANCE (``acme_batch_set_measurement_per_instance``) instead of ``f0``: ``f_den`` with ``f_num``,
+        a scalar or N integers -- instance i correlates with f_num[i] / f_den of the sample rate --, or
+        ``f0_from_source=row``: the ``f_den`` / ``f_num`` of the sine source armed on input row ``row`` (``set_source``).  A
+        window of ``length=f_den`` samples holds whole periods of every instance's fundamental."""
+        if f0_from_source is not None:
+            if f0 is not None or f_num is not None or f_den is not None:
+                raise ValueError("f0_from_source excludes f0 and f_den / f_num")
+            src = self._sources.get(int(f0_from_source))
+            if src != SOURCE_SINE:
+                raise ValueError(f"input row {f0_from_source} has no sine source to take the fundamental from")
+            f_den, f_num = self._sine[int(f0_from_source)]
+        if f_num is None and f_den is None:
+            spec, rows = measure_spec(self.model.ny, start, length, f0, harmonics, rows)
+            self.lib.check(self.lib.L.acme_batch_set_measurement(self.h, *spec))
+        else:
+            if f0 is not None:
+                raise ValueError("f0 and f_den / f_num exclude each other: one fundamental, or one per instance")
+            if f_num is None or f_den is None:
+                raise ValueError("per-instance fundamentals need both f_den and f_num")
+            spec, rows = measure_spec(self.model.ny, start, length, (0, int(f_den)), harmonics, rows)
+            fa, fp = self._per_instance(f_num, np.int64, "f_num")
+            self.lib.check(self.lib.L.acme_batch_set_measurement_per_instance(self.h, spec[0], spec[1], int(f_den), fp,
+                                                                              spec[4], spec[5]))
         self._meas = (int(harmonics), rows)
         return self
+
+    def measurement_plan(self):
+        """The plan of the armed per-instance measurement (``acme_batch_get_measurement_plan``): a dict with ``groups``
+        (distinct f_num), ``chunk`` (samples per step), ``perm`` (lane slot -> pair) and ``wave_group`` (per wave of 64
+        slots its one group -- the broadcast loop --, or -1: a mixed wave of per-lane loads)."""
+        if self._meas is None:
+            raise AcmeError("no measurement is armed")
+        P = self.n * len(self._meas[1])
+        perm, wg = np.zeros(P, dtype=np.int64), np.zeros((P + 63) // 64, dtype=np.int32)
+        F, chunk = C.c_longlong(0), C.c_longlong(0)
+        self.lib.check(self.lib.L.acme_batch_get_measurement_plan(
+            self.h, C.byref(F), C.byref(chunk), perm.ctypes.data_as(C.POINTER(C.c_longlong)), _ip(wg)))
+        return dict(groups=F.value, chunk=chunk.value, perm=perm, wave_group=wg)
 
     def clear_measurement(self):
         """switch the measurement off (``acme_batch_clear_measurement``)"""
@@ -495,11 +536,14 @@ class ModelRunner:
             fa, fp = self._per_instance(f_num, np.int64, "f_num")
             pa, pp = self._per_instance(phase, np.int64, "phase")
             self.lib.check(L.acme_batch_set_source_sine(self.h, int(row), int(f_den), fp, pp, ap, op))
+            self._sine[int(row)] = (int(f_den), 0 if fa is None else fa.copy())
         else:
             if table is None:
                 raise ValueError("a table source needs a table")
             w = np.ascontiguousarray(np.asarray(table, dtype=np.float64).ravel())
             self.lib.check(L.acme_batch_set_source_table(self.h, int(row), _dp(w), len(w), ap, op))
+        if k != SOURCE_SINE:
+            self._sine.pop(int(row), None)
         self._sources[int(row)] = k
         return self
 
@@ -507,9 +551,10 @@ class ModelRunner:
         """the row is the caller's again (``acme_batch_clear_source``); ``row=-1``: every row"""
         self.lib.check(self.lib.L.acme_batch_clear_source(self.h, int(row)))
         if row < 0:
-            self._sources = {}
+            self._sources, self._sine = {}, {}
         else:
             self._sources.pop(int(row), None)
+            self._sine.pop(int(row), None)
         return self
 
     @property
@@ -956,11 +1001,14 @@ class MultiDeviceRunner:
                 r.set_oversampling(factor, up, down, held_rows)
         return self
 
-    def set_measurement(self, start=0, length=0, f0=None, harmonics=0, rows=None):
-        """``ModelRunner.set_measurement`` on every device's batch"""
-        for r in self.runners:
+    def set_measurement(self, start=0, length=0, f0=None, harmonics=0, rows=None, f_den=None, f_num=None, f0_from_source=None):
+        """``ModelRunner.set_measurement`` on every device's batch, per-instance ``f_num`` sliced over the devices"""
+        if f_num is not None and np.ndim(f_num) != 0 and len(f_num) != self.n:
+            raise DimensionMismatch(f"per-instance fundamentals need {self.n} values")
+        for r, (lo, hi) in zip(self.runners, self.ranges):
             if r is not None:
-                r.set_measurement(start, length, f0, harmonics, rows)
+                part = f_num if f_num is None or np.ndim(f_num) == 0 else np.asarray(f_num)[lo:hi]
+                r.set_measurement(start, length, f0, harmonics, rows, f_den, part, f0_from_source)
         return self
 
     def reset_measurement(self):

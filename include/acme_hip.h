@@ -262,6 +262,31 @@ int acme_batch_set_oversampling(acme_batch *b, int factor, const double *h_up, i
  * as plain arguments, not as a struct: a binding needs no mirror of the layout.) */
 int acme_batch_set_measurement(acme_batch *b, long long start, long long length, long long f_num, long long f_den,
                                int harmonics, unsigned long long rows);
+/* arm a measurement with a fundamental PER INSTANCE: the semantics of acme_batch_set_measurement with f_num replaced by
+ * f_num[i] for instance i -- a frequency sweep driven by a per-instance sine source (below) is MEASURED in the same batch: a
+ * Bode plot, THD against frequency, a drive x frequency grid, without [N][T][ny] anywhere.
+ *   f_den, f_num    fundamental of instance i = f_num[i] / f_den x the base sample rate; f_num: a HOST array of N entries,
+ *                   0 <= f_num[i] < f_den < 2^31, copied by the call (only read)
+ * The formulas are the ones above with f_num -> f_num[i]: th = 2 pi (((h f_num[i]) mod f_den (m mod f_den)) mod f_den) / f_den,
+ * the same cos / sin of the same angle, each accumulator ONE chain in sample order.  With every f_num[i] = f the results
+ * are, bit for bit, those of acme_batch_set_measurement(f, f_den); instance i's results are, bit for bit, those of the
+ * shared form at f_num[i].  acme_batch_get_measurement (out[N][nrows][4 + 2H], unchanged), _reset_measurement (the
+ * frequencies stay) and _clear_measurement work as on any measurement; arming either form replaces the other;
+ * acme_batch_set_matrices carries the frequencies with the accumulators.  Validates as the shared form does
+ * (ACME_ERR_INVALID; an f_num[i] out of range is named by its instance); not together with acme_batch_set_isolation.
+ * WHICH WINDOW: length = f_den samples hold whole periods of EVERY instance's fundamental (instance i: f_num[i] of them), and
+ * so does every multiple of f_den / gcd(f_den, f_num[0], ..., f_num[N - 1]): that is the window of a sweep, after a start
+ * that lets the transient die.
+ * The instances are grouped by distinct f_num (csrc/acme_measure.h); a step's twiddle table takes at most 64 MiB, or one
+ * tile of 64 samples per group and harmonic where that is more.  Test hook: ACME_MEAS_TABLE_BUDGET=bytes in the environment
+ * at arming replaces the 64 MiB (results do not depend on it). */
+int acme_batch_set_measurement_per_instance(acme_batch *b, long long start, long long length, long long f_den,
+                                            long long *f_num /* host, [N], only read */, int harmonics,
+                                            unsigned long long rows);
+/* the plan of the armed per-instance measurement (tests, probes; any pointer may be NULL): *n_groups distinct f_num, *chunk
+ * samples per step, perm[N nrows]: lane slot -> pair (i nrows + j), wave_group[(N nrows + 63) / 64]: the one group of the 64
+ * slots' wave (the broadcast loop), or -1 (mixed: per-lane loads).  ACME_ERR_INVALID while no such measurement is armed. */
+int acme_batch_get_measurement_plan(acme_batch *b, long long *n_groups, long long *chunk, long long *perm, int *wave_group);
 /* switch the measurement off (y = NULL is refused again) */
 int acme_batch_clear_measurement(acme_batch *b);
 /* zero the accumulators and restart the window's clock (the armed parameters stay) */

@@ -35,7 +35,7 @@ import ACME: run!, solve, hasconverged, needediterations, set_resabstol!,
              get_extrapolation_origin, set_extrapolation_origin, get_extrapolation_jacobian
 
 export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host_buffers!, release_host_buffers!, set_isolation!, set_balance!,
-       MeasureSpec, Measurement, set_measurement!, clear_measurement!, reset_measurement!, measurement, measure!,
+       MeasureSpec, Measurement, set_measurement!, clear_measurement!, reset_measurement!, measurement, measurement_plan, measure!,
        set_source!, clear_source!, source_clock, source_clock!, run_sources!, render_sources
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
@@ -474,7 +474,46 @@ function set_measurement!(r::BatchRunner, spec::MeasureSpec)
     r.meas = spec
     return r
 end
-set_measurement!(r::BatchRunner; kwargs...) = set_measurement!(r, MeasureSpec(; kwargs...))
+function set_measurement!(r::BatchRunner; f_den=nothing, f_num=nothing, kwargs...)
+    f_num === nothing && f_den === nothing && return set_measurement!(r, MeasureSpec(; kwargs...))
+    (f_num === nothing || f_den === nothing) && error("per-instance fundamentals need both f_den and f_num")
+    haskey(kwargs, :f0) && error("f0 and f_den / f_num exclude each other")
+    return set_measurement!(r, MeasureSpec(; f0=0 // Int64(f_den), kwargs...), Int64(f_den), convert(Vector{Int64}, f_num))
+end
+
+"""
+    set_measurement!(runner; start=0, length=0, harmonics=0, rows=(), f_den, f_num::Vector{Int64})
+
+Arm a measurement with a fundamental PER INSTANCE (`acme_batch_set_measurement_per_instance`): instance `i` correlates with
+`f_num[i] / f_den` of the sample rate -- the batch a per-instance sine source drives as a frequency sweep is measured as
+one.  A window of `length = f_den` samples holds whole periods of every instance's fundamental.
+"""
+function set_measurement!(r::BatchRunner, spec::MeasureSpec, f_den::Int64, f_num::Vector{Int64})
+    length(f_num) == r.n || throw(DimensionMismatch("f_num needs one entry per instance ($(r.n))"))
+    GC.@preserve f_num check(ccall((:acme_batch_set_measurement_per_instance, lib), Cint,
+                (Ptr{Cvoid}, Clonglong, Clonglong, Clonglong, Ptr{Clonglong}, Cint, Culonglong),
+                r.h, spec.start, spec.length, f_den, f_num, spec.harmonics, spec.rows))
+    r.meas = spec
+    return r
+end
+
+"""
+    measurement_plan(runner) -> (groups, chunk, perm, wave_group)
+
+The plan of the armed per-instance measurement (`acme_batch_get_measurement_plan`): distinct frequencies, samples per
+step, lane slot -> pair (0-based), and per wave of 64 slots its one group or -1 (a mixed wave).
+"""
+function measurement_plan(r::BatchRunner)
+    spec = r.meas
+    spec === nothing && error("no measurement is armed")
+    ny = ACME.ny(r.model)
+    P = r.n * (spec.rows == 0 ? min(ny, 64) : count_ones(spec.rows))
+    perm, wg = Vector{Int64}(undef, P), Vector{Cint}(undef, cld(P, 64))
+    groups, chunk = Ref{Clonglong}(0), Ref{Clonglong}(0)
+    check(ccall((:acme_batch_get_measurement_plan, lib), Cint,
+                (Ptr{Cvoid}, Ref{Clonglong}, Ref{Clonglong}, Ptr{Clonglong}, Ptr{Cint}), r.h, groups, chunk, perm, wg))
+    return (groups=groups[], chunk=chunk[], perm=perm, wave_group=wg)
+end
 
 "switch the measurement off (`acme_batch_clear_measurement`)"
 function clear_measurement!(r::BatchRunner)
