@@ -156,6 +156,9 @@ struct acme_batch {
         std::vector<int> wgrp;
         long long *d_fnum_g = nullptr, *d_perm = nullptr;       // [F], [N nrows]
         int *d_sgrp = nullptr, *d_wgrp = nullptr;               // [N nrows], [(N nrows + 63) / 64]
+        // bins (acme_batch_set_measurement_bins): the per-instance plan over groups of distinct tone tuples, H = the bins
+        bool bins = false;
+        long long *d_kbin_g = nullptr;           // [F][H]: the groups' reduced bin frequencies
     } meas;
     // Input rows generated on the device (acme_batch_set_source_*, acme_source.h): the rows' descriptions and per-instance
     // parameters in device memory, the source clock
@@ -736,6 +739,7 @@ int acme_batch_release_host_buffers(acme_batch *b) {
 static void meas_release(acme_batch::Measurement &M) {
     (void)be::dfree(M.d_acc); (void)be::dfree(M.d_tw); (void)be::dfree(M.d_ys);
     (void)be::dfree(M.d_fnum_g); (void)be::dfree(M.d_perm); (void)be::dfree(M.d_sgrp); (void)be::dfree(M.d_wgrp);
+    (void)be::dfree(M.d_kbin_g);
     M = acme_batch::Measurement{};
 }
 
@@ -1293,6 +1297,11 @@ static int meas_step(acme_batch *b, const double *y, long long n, long long pitc
         const long long len = hi - s < M.chunk ? hi - s : M.chunk;
         MeasArgs A{y, M.d_acc, M.d_tw, b->N, len, pitch, s - M.pos, b->P.actual.ny, M.nrows, M.H, {}};
         memcpy(A.row, M.row, sizeof(A.row));
+        if (M.bins) {
+            const MeasBinsTwArgs W{M.d_tw, M.d_kbin_g, s - M.start, len, M.f_den, M.H, M.F};
+            HIPCHK(meas_bins_launch(W, MeasPiArgs{A, M.d_perm, M.d_sgrp, M.d_wgrp}, st));
+            continue;
+        }
         if (M.pi) {
             const MeasPiTwArgs W{M.d_tw, M.d_fnum_g, s - M.start, len, M.f_den, M.H, M.F};
             HIPCHK(meas_pi_launch(W, MeasPiArgs{A, M.d_perm, M.d_sgrp, M.d_wgrp}, st));
@@ -1838,15 +1847,30 @@ static int src_commit(acme_batch *b) {
     if (!S.armed) S.clock = 0;
     return ACME_OK;
 }
-// kind, den (SINE: f_den; TABLE: P), the arrays of the kind (host arrays of N entries, w of P; NULL = default)
+// kind, den (SINE, MULTISINE: f_den; TABLE: P), the arrays of the kind (host arrays of N entries, w of P; NULL = default;
+// MULTISINE: f_num, phase and amp hold tones x N entries)
 static int set_source(acme_batch *b, int row, int kind, long long den, const long long *f_num, const long long *phase,
-                      const double *w, const double *amp, const double *offset) {
+                      const double *w, const double *amp, const double *offset, int tones = 1) {
     join_worker(b);
     if (!b) return fail(ACME_ERR_INVALID, "null batch");
     const int nu = b->P.actual.nu;
     if (nu > 64) return fail(ACME_ERR_UNSUPPORTED, "sources: more than 64 input rows");
     if (row < 0 || row >= nu) return fail(ACME_ERR_INVALID, "source: row beyond the model's inputs");
     const size_t N = (size_t)b->N;
+    if (kind == SRC_MULTISINE) {
+        if (tones < 1 || tones > SRC_MAX_TONES) return fail(ACME_ERR_INVALID, "multisine source: tones must be 1 ... 4");
+        if (!f_num) return fail(ACME_ERR_INVALID, "multisine source: null f_num");
+        if (den <= 0 || den >= (1ll << 31)) return fail(ACME_ERR_INVALID, "multisine source: f_den must be 1 ... 2^31 - 1");
+        for (int k = 0; k < tones; ++k)
+            for (size_t i = 0; i < N; ++i) {
+                const size_t e = (size_t)k * N + i;
+                if (f_num[e] < 0 || f_num[e] >= den || (phase && (phase[e] < 0 || phase[e] >= den)))
+                    return fail(ACME_ERR_INVALID, "multisine source: f_num and phase must be 0 ... f_den - 1 (tone " + std::to_string(k) +
+                                                      ", instance " + std::to_string(i) + ")");
+                if (amp && !std::isfinite(amp[e]))
+                    return fail(ACME_ERR_INVALID, "source: non-finite amp (tone " + std::to_string(k) + ", instance " + std::to_string(i) + ")");
+            }
+    }
     if (kind == SRC_SINE) {
         if (den <= 0 || den >= (1ll << 31)) return fail(ACME_ERR_INVALID, "sine source: f_den must be 1 ... 2^31 - 1");
         for (size_t i = 0; i < N; ++i)
@@ -1857,8 +1881,9 @@ static int set_source(acme_batch *b, int row, int kind, long long den, const lon
         if (den < 1 || den > SRC_MAX_TABLE) return fail(ACME_ERR_INVALID, "table source: P must be 1 ... 2^24");
         if (!w) return fail(ACME_ERR_INVALID, "table source: null table");
     }
+    const double *amp_n = kind == SRC_MULTISINE ? nullptr : amp;       // (MULTISINE: tones x N amplitudes, checked with their tones above)
     for (size_t i = 0; i < N; ++i)
-        if ((amp && !std::isfinite(amp[i])) || (offset && !std::isfinite(offset[i])))
+        if ((amp_n && !std::isfinite(amp_n[i])) || (offset && !std::isfinite(offset[i])))
             return fail(ACME_ERR_INVALID, "source: non-finite amp or offset (instance " + std::to_string(i) + ")");
     if (b->iso_thr > 0.0)
         return fail(ACME_ERR_UNSUPPORTED, "sources are not available while the isolation of slow instances is in force");
@@ -1868,10 +1893,13 @@ static int set_source(acme_batch *b, int row, int kind, long long den, const lon
     SrcRow R{};
     R.kind = kind;
     R.den = kind == SRC_CONST ? 1 : den;
+    R.tones = kind == SRC_MULTISINE ? tones : 0;
+    const size_t NT = kind == SRC_MULTISINE ? N * (size_t)tones : N;
+    const bool sine = kind == SRC_SINE || kind == SRC_MULTISINE;
     int rc = src_upload(offset, sizeof(double) * N, (const void **)&R.off);
-    if (rc == ACME_OK && kind != SRC_CONST) rc = src_upload(amp, sizeof(double) * N, (const void **)&R.amp);
-    if (rc == ACME_OK && kind == SRC_SINE) rc = src_upload(f_num, sizeof(long long) * N, (const void **)&R.fnum);
-    if (rc == ACME_OK && kind == SRC_SINE) rc = src_upload(phase, sizeof(long long) * N, (const void **)&R.phase);
+    if (rc == ACME_OK && kind != SRC_CONST) rc = src_upload(amp, sizeof(double) * NT, (const void **)&R.amp);
+    if (rc == ACME_OK && sine) rc = src_upload(f_num, sizeof(long long) * NT, (const void **)&R.fnum);
+    if (rc == ACME_OK && sine) rc = src_upload(phase, sizeof(long long) * NT, (const void **)&R.phase);
     if (rc == ACME_OK && kind == SRC_TABLE) rc = src_upload(w, sizeof(double) * (size_t)den, (const void **)&R.w);
     for (auto &e : b->os.ev) if (rc == ACME_OK && !e && be::event_create(&e) != 0) rc = fail(ACME_ERR_HIP, "hipEventCreate");      // (the host pipeline of run_os)
     if (rc != ACME_OK) {
@@ -1899,6 +1927,10 @@ int acme_batch_set_source_sine(acme_batch *b, int row, long long f_den, long lon
 }
 int acme_batch_set_source_table(acme_batch *b, int row, const double *w, long long P, const double *amp, const double *offset) {
     return set_source(b, row, SRC_TABLE, P, nullptr, nullptr, w, amp, offset);
+}
+int acme_batch_set_source_multisine(acme_batch *b, int row, long long f_den, int tones, long long *f_num, long long *phase,
+                                    const double *amp, const double *offset) {
+    return set_source(b, row, SRC_MULTISINE, f_den, f_num, phase, nullptr, amp, offset, tones);
 }
 
 int acme_batch_clear_source(acme_batch *b, int row) {
@@ -2096,17 +2128,51 @@ static int meas_zero(acme_batch *b) {
 
 // per-instance fundamentals: the instances grouped by distinct f_num, the plan (acme_measure.h) to the device.  The table's
 // budget is MEAS_PI_BUDGET; ACME_MEAS_TABLE_BUDGET (bytes) in the environment overrides it (tests: chunks of one tile)
+// fg: what the twiddle kernel reads per group ([F] f_num; bins: [F][H] reduced bin frequencies), grp: instance -> group
+static int meas_plan_arm(acme_batch *b, const std::vector<long long> &fg, const std::vector<int> &grp, int F, long long **d_fg);
 static int meas_pi_arm(acme_batch *b, const long long *f_num) {
     acme_batch::Measurement &M = b->meas;
     const size_t N = (size_t)b->N;
     std::vector<long long> fg(f_num, f_num + N);
     std::sort(fg.begin(), fg.end());
     fg.erase(std::unique(fg.begin(), fg.end()), fg.end());
-    std::vector<int> grp(N), sgrp;
+    std::vector<int> grp(N);
     for (size_t i = 0; i < N; ++i) grp[i] = (int)(std::lower_bound(fg.begin(), fg.end(), f_num[i]) - fg.begin());
-    M.pi = true;
-    M.F = (int)fg.size();
     M.f_num = fg.empty() ? 0 : fg[0];
+    return meas_plan_arm(b, fg, grp, (int)fg.size(), &M.d_fnum_g);
+}
+// bins: the instances grouped by distinct tone tuple (f_num[0][i], ...) in lexicographic order; per group and bin the reduced
+// frequency k = (sum_j coef[b][j] f_num[j]) mod f_den, the non-negative residue (|coef| <= 32767, f_num < 2^31: |sum| < 2^48)
+static int meas_bins_arm(acme_batch *b, int tones, const long long *f_num, const int *coef) {
+    acme_batch::Measurement &M = b->meas;
+    const size_t N = (size_t)b->N;
+    typedef std::array<long long, 4> Tup;
+    std::vector<Tup> tg(N);
+    for (size_t i = 0; i < N; ++i) {
+        tg[i] = Tup{0, 0, 0, 0};
+        for (int j = 0; j < tones; ++j) tg[i][(size_t)j] = f_num[(size_t)j * N + i];
+    }
+    const std::vector<Tup> all = tg;
+    std::sort(tg.begin(), tg.end());
+    tg.erase(std::unique(tg.begin(), tg.end()), tg.end());
+    std::vector<int> grp(N);
+    for (size_t i = 0; i < N; ++i) grp[i] = (int)(std::lower_bound(tg.begin(), tg.end(), all[i]) - tg.begin());
+    std::vector<long long> kb(tg.size() * (size_t)M.H);
+    for (size_t g = 0; g < tg.size(); ++g)
+        for (int q = 0; q < M.H; ++q) {
+            long long k = 0;
+            for (int j = 0; j < tones; ++j) k += (long long)coef[q * tones + j] * tg[g][(size_t)j];
+            k %= M.f_den;
+            kb[g * (size_t)M.H + (size_t)q] = k < 0 ? k + M.f_den : k;
+        }
+    M.bins = true;
+    return meas_plan_arm(b, kb, grp, (int)tg.size(), &M.d_kbin_g);
+}
+static int meas_plan_arm(acme_batch *b, const std::vector<long long> &fg, const std::vector<int> &grp, int F, long long **d_fg) {
+    acme_batch::Measurement &M = b->meas;
+    std::vector<int> sgrp;
+    M.pi = true;
+    M.F = F;
     long long budget = MEAS_PI_BUDGET;
     if (const char *e = getenv("ACME_MEAS_TABLE_BUDGET")) { const long long v = atoll(e); if (v >= 1) budget = v; }
     M.chunk = meas_pi_chunk(M.F > 0 ? M.F : 1, M.H, budget);
@@ -2117,7 +2183,7 @@ static int meas_pi_arm(acme_batch *b, const long long *f_num) {
         HIPCHK(be::copy_h2d(*d, v.data(), sizeof(v[0]) * v.size()));
         return ACME_OK;
     };
-    int rc = put(&M.d_fnum_g, fg);
+    int rc = put(d_fg, fg);
     if (rc == ACME_OK) rc = put(&M.d_perm, M.perm);
     if (rc == ACME_OK) rc = put(&M.d_sgrp, sgrp);
     if (rc == ACME_OK) rc = put(&M.d_wgrp, M.wgrp);
@@ -2126,7 +2192,9 @@ static int meas_pi_arm(acme_batch *b, const long long *f_num) {
 
 // spec = nullptr: off
 // f_num_i != nullptr: per-instance fundamentals, host [N]
-struct MeasSpec { long long start, length, f_num, f_den; int harmonics; unsigned long long rows; const long long *f_num_i; };
+// tones > 0: bins -- f_num_i host [tones][N], coef host [harmonics][tones]
+struct MeasSpec { long long start, length, f_num, f_den; int harmonics; unsigned long long rows; const long long *f_num_i;
+                  int tones; const int *coef; };
 static int set_measurement(acme_batch *b, const MeasSpec *spec) {
     join_worker(b);
     if (!b) return fail(ACME_ERR_INVALID, "null batch");
@@ -2143,9 +2211,17 @@ static int set_measurement(acme_batch *b, const MeasSpec *spec) {
         const unsigned long long rows = spec->rows ? spec->rows : ny >= 64 ? ~0ull : ((1ull << ny) - 1ull);
         for (int r = 0; r < 64 && r < ny; ++r)
             if (rows >> r & 1ull) row[nrows++] = (unsigned char)r;
-        for (long long i = 0; spec->f_num_i && i < b->N; ++i)
+        for (long long i = 0; spec->f_num_i && !spec->tones && i < b->N; ++i)
             if (spec->f_num_i[i] < 0 || spec->f_num_i[i] >= spec->f_den)
                 return fail(ACME_ERR_INVALID, "measurement: f_num of instance " + std::to_string(i) + " is outside 0 ... f_den - 1");
+        for (int j = 0; j < spec->tones; ++j)
+            for (long long i = 0; i < b->N; ++i)
+                if (spec->f_num_i[j * b->N + i] < 0 || spec->f_num_i[j * b->N + i] >= spec->f_den)
+                    return fail(ACME_ERR_INVALID, "measurement: f_num of tone " + std::to_string(j) + ", instance " + std::to_string(i) +
+                                                      " is outside 0 ... f_den - 1");
+        for (int q = 0; spec->tones && q < spec->harmonics * spec->tones; ++q)
+            if (spec->coef[q] < -32767 || spec->coef[q] > 32767)
+                return fail(ACME_ERR_INVALID, "measurement: a coefficient of bin " + std::to_string(q / spec->tones) + " is outside -32767 ... 32767");
         if (b->iso_thr > 0.0)
             return fail(ACME_ERR_UNSUPPORTED, "measurements are not available while the isolation of slow instances is in force");
     }
@@ -2164,7 +2240,7 @@ static int set_measurement(acme_batch *b, const MeasSpec *spec) {
     memcpy(M.row, row, sizeof(row));
     HIPCHK(be::dmalloc((void **)&M.d_acc, sizeof(double) * (size_t)(4 + 2 * M.H) * (size_t)b->N * nrows));
     if (spec->f_num_i) {
-        const int rc = meas_pi_arm(b, spec->f_num_i);
+        const int rc = spec->tones ? meas_bins_arm(b, spec->tones, spec->f_num_i, spec->coef) : meas_pi_arm(b, spec->f_num_i);
         if (rc != ACME_OK) { meas_release(M); return rc; }
     }
     HIPCHK(be::dmalloc((void **)&M.d_tw, sizeof(double) * 2 * (size_t)(M.pi ? M.F : 1) * (size_t)M.H * (size_t)M.chunk));
@@ -2177,14 +2253,24 @@ static int set_measurement(acme_batch *b, const MeasSpec *spec) {
 
 int acme_batch_set_measurement(acme_batch *b, long long start, long long length, long long f_num, long long f_den,
                                int harmonics, unsigned long long rows) {
-    const MeasSpec spec{start, length, f_num, f_den, harmonics, rows, nullptr};
+    const MeasSpec spec{start, length, f_num, f_den, harmonics, rows, nullptr, 0, nullptr};
     return set_measurement(b, &spec);
 }
 
 int acme_batch_set_measurement_per_instance(acme_batch *b, long long start, long long length, long long f_den,
                                             long long *f_num, int harmonics, unsigned long long rows) {
     if (b && !f_num) return fail(ACME_ERR_INVALID, "measurement: null f_num");
-    const MeasSpec spec{start, length, 0, f_den, harmonics, rows, f_num};
+    const MeasSpec spec{start, length, 0, f_den, harmonics, rows, f_num, 0, nullptr};
+    return set_measurement(b, &spec);
+}
+
+int acme_batch_set_measurement_bins(acme_batch *b, long long start, long long length, long long f_den, int tones, long long *f_num,
+                                    int bins, const int *coef, unsigned long long rows) {
+    if (b && (tones < 1 || tones > SRC_MAX_TONES)) return fail(ACME_ERR_INVALID, "measurement: tones must be 1 ... 4");
+    if (b && !f_num) return fail(ACME_ERR_INVALID, "measurement: null f_num");
+    if (b && (bins < 0 || bins > MEAS_MAX_H)) return fail(ACME_ERR_INVALID, "measurement: bins must be 0 ... 32");
+    if (b && bins > 0 && !coef) return fail(ACME_ERR_INVALID, "measurement: null coef");
+    const MeasSpec spec{start, length, 0, f_den, bins, rows, f_num, tones, coef};
     return set_measurement(b, &spec);
 }
 

@@ -33,9 +33,18 @@
 // Unit 0 (the moments) does not read the table: the same chain, the same bits.  F = 1 is the shared layout with one more
 // indirection; F = N is mixed waves throughout with no idle lanes.
 //
+// BINS (acme_batch_set_measurement_bins): instance i has `tones` frequencies f_num[j][i] / f_den and bin b correlates with the
+// integer combination k[b][i] = (sum_j coef[b][j] f_num[j][i]) mod f_den (the non-negative residue, formed on the host in
+// exact 64-bit integers) -- the sum and difference products of a two-tone test.  The instances are grouped by distinct tone
+// tuple, the table [F][B][len] is written from the groups' reduced bins kbin_g[F][B] (meas_bins_tw: meas_twiddle(1, m, k,
+// f_den), the very twiddle of the shared form at f_num = k with one harmonic), and the plan, the budget, the chunk rule and
+// acme_meas_pi_kernel with H = B are the per-instance form's, unchanged.
+//
 // The per-element functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with g++).
 #pragma once
+#include <algorithm>
+#include <array>
 #include <climits>
 #include <cmath>
 #include <vector>
@@ -79,6 +88,14 @@ struct MeasPiTwArgs {
     int H, F;
 };
 
+// bins: the groups' reduced bin frequencies beside the table (A.tw: [F][B][len] pairs)
+struct MeasBinsTwArgs {
+    double *tw;                 // [F][B][len] pairs (cos, sin) of samples m0 ... m0 + len - 1 (window-relative)
+    const long long *kbin_g;    // [F][B]: 0 <= k < f_den
+    long long m0, len, f_den;
+    int B, F;
+};
+
 constexpr long long MEAS_PI_BUDGET = 64ll << 20;    // bytes of twiddle table a chunk may take (one tile is always allowed)
 
 // cos / sin of 2 pi ((h f_num m) mod f_den) / f_den, the phase reduced exactly (h <= 32, f_den < 2^31: products < 2^62)
@@ -107,6 +124,12 @@ ACME_HD inline void meas_pi_tw(const MeasPiTwArgs &A, long long idx) {
     const long long per = A.H * A.len, g = idx / per, r = idx - g * per;
     const long long h = r / A.len, t = r - h * A.len;
     meas_twiddle(h + 1, A.m0 + t, A.fnum_g[g], A.f_den, &A.tw[2 * idx], &A.tw[2 * idx + 1]);
+}
+
+ACME_HD inline void meas_bins_tw(const MeasBinsTwArgs &A, long long idx) {
+    const long long per = A.B * A.len, g = idx / per, r = idx - g * per;
+    const long long b = r / A.len, t = r - b * A.len;
+    meas_twiddle(1, A.m0 + t, A.kbin_g[g * A.B + b], A.f_den, &A.tw[2 * idx], &A.tw[2 * idx + 1]);
 }
 
 // NaN sticks: once an accumulator is NaN it stays so
@@ -374,6 +397,10 @@ __global__ __launch_bounds__(1024) void acme_meas_pi_kernel(acme::MeasPiArgs B) 
         if (u == 0) { A.acc[2 * P + p] = a2; A.acc[3 * P + p] = a3; }
     }
 }
+__global__ __launch_bounds__(256) void acme_meas_bins_tw_kernel(acme::MeasBinsTwArgs A) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx < (long long)A.F * A.B * A.len) acme::meas_bins_tw(A, idx);
+}
 namespace acme {
 inline int meas_launch(const MeasTwArgs &T, const MeasArgs &A, hipStream_t st) {
     if (A.H > 0) {
@@ -387,6 +414,15 @@ inline int meas_launch(const MeasTwArgs &T, const MeasArgs &A, hipStream_t st) {
     hipLaunchKernelGGL(acme_meas_kernel, dim3((unsigned)((P + 63) / 64), (unsigned)groups), dim3(64 * waves), 0, st, A);
     return (int)hipGetLastError();
 }
+// the per-instance kernel on a table that is written: shared by the per-instance form and the bins
+inline int meas_pi_run(const MeasPiArgs &B, hipStream_t st) {
+    const MeasArgs &A = B.A;
+    int waves = 1, groups = 1;
+    meas_shape(A.H, &waves, &groups);
+    const long long P = A.n * A.nrows;
+    hipLaunchKernelGGL(acme_meas_pi_kernel, dim3((unsigned)((P + 63) / 64), (unsigned)groups), dim3(64 * waves), 0, st, B);
+    return (int)hipGetLastError();
+}
 inline int meas_pi_launch(const MeasPiTwArgs &T, const MeasPiArgs &B, hipStream_t st) {
     const MeasArgs &A = B.A;
     if (A.H > 0) {
@@ -395,11 +431,18 @@ inline int meas_pi_launch(const MeasPiTwArgs &T, const MeasPiArgs &B, hipStream_
         const int e = (int)hipGetLastError();
         if (e) return e;
     }
-    int waves = 1, groups = 1;
-    meas_shape(A.H, &waves, &groups);
-    const long long P = A.n * A.nrows;
-    hipLaunchKernelGGL(acme_meas_pi_kernel, dim3((unsigned)((P + 63) / 64), (unsigned)groups), dim3(64 * waves), 0, st, B);
-    return (int)hipGetLastError();
+    return meas_pi_run(B, st);
+}
+// bins: the table from the groups' reduced bins, then the per-instance kernel with H = B
+inline int meas_bins_launch(const MeasBinsTwArgs &T, const MeasPiArgs &B, hipStream_t st) {
+    const MeasArgs &A = B.A;
+    if (A.H > 0) {
+        const long long total = (long long)T.F * A.H * A.len;
+        hipLaunchKernelGGL(acme_meas_bins_tw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, T);
+        const int e = (int)hipGetLastError();
+        if (e) return e;
+    }
+    return meas_pi_run(B, st);
 }
 }  // namespace acme
 #else
@@ -411,14 +454,21 @@ inline int meas_launch(const MeasTwArgs &T, const MeasArgs &A, void *) {
     return 0;
 }
 // slot by slot through the plan, every unit's chain on the table row of the slot's group
-inline int meas_pi_launch(const MeasPiTwArgs &T, const MeasPiArgs &B, void *) {
-    for (long long idx = 0; idx < (long long)T.F * B.A.H * B.A.len; ++idx) meas_pi_tw(T, idx);
+inline int meas_pi_run(const MeasPiArgs &B) {
     for (long long q = 0; q < B.A.n * B.A.nrows; ++q) {
         MeasArgs A = B.A;
         A.tw = B.A.tw + 2 * (long long)B.sgrp[q] * A.H * A.len;
         for (int u = 0; u <= A.H; ++u) meas_chain(A, B.perm[q], u);
     }
     return 0;
+}
+inline int meas_pi_launch(const MeasPiTwArgs &T, const MeasPiArgs &B, void *) {
+    for (long long idx = 0; idx < (long long)T.F * B.A.H * B.A.len; ++idx) meas_pi_tw(T, idx);
+    return meas_pi_run(B);
+}
+inline int meas_bins_launch(const MeasBinsTwArgs &T, const MeasPiArgs &B, void *) {
+    for (long long idx = 0; idx < (long long)T.F * B.A.H * B.A.len; ++idx) meas_bins_tw(T, idx);
+    return meas_pi_run(B);
 }
 }  // namespace acme
 #endif

@@ -6,6 +6,9 @@
 //           (-f_den / 2, f_den / 2]: the phase reduced exactly in 64-bit integers, the angle formed as meas_twiddle forms
 //           it (phase_angle, acme_measure.h)
 //   TABLE   fma(amp_i, w[n mod P], offset_i)
+//   MULTISINE  a sum of 1 ... SRC_MAX_TONES sines as ONE chain in tone order: v = offset_i, then v = fma(amp_ki, sin(th_k), v)
+//           for k = 0 ... tones - 1, each th_k reduced and formed as SINE's from f_num_ki, phase_ki (per-tone arrays [tones][N]);
+//           one tone is the SINE row bit for bit
 //
 // One launch per time slice (acme_api.inc run_os, where the expand kernel sits for constant rows) writes the slice's full
 // [N][len][nu] block: sourced rows generated, the others gathered from the caller's rows.
@@ -19,7 +22,9 @@
 // below 2^62); from there kappa += step with one conditional subtraction per sample -- the integers are exact, so every
 // sample's kappa is the closed form's.  Table rows: the tile's window of w (min(tile, P) entries, the same for every
 // instance) is staged in LDS once per block while the rows' windows fit SRC_LDS doubles; rows beyond that read w from
-// HBM / L2.
+// HBM / L2.  A MULTISINE row keeps one kappa and one step PER TONE (the same two reductions per tone and instance, the same
+// conditional subtraction per tone and sample); a launch with such a row takes the kernel's second instantiation
+// (src_thread<true>, acme_source_multi_kernel: src_plan decides), every other launch the one it always took.
 //
 // The per-thread functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops over (block, thread) otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with
@@ -34,7 +39,8 @@
 
 namespace acme {
 
-constexpr int SRC_NONE = 0, SRC_CONST = 1, SRC_SINE = 2, SRC_TABLE = 3;      // (include/acme_hip.h: ACME_SOURCE_*)
+constexpr int SRC_NONE = 0, SRC_CONST = 1, SRC_SINE = 2, SRC_TABLE = 3, SRC_MULTISINE = 4;     // (include/acme_hip.h: ACME_SOURCE_*)
+constexpr int SRC_MAX_TONES = 4;            // tones of a MULTISINE row (ACME_MAX_SOURCE_TONES)
 constexpr long long SRC_MAX_TABLE = 1ll << 24;
 constexpr int SRC_BLOCK = 256;              // threads per block
 constexpr int SRC_TILE = 4096;              // samples per block
@@ -45,10 +51,11 @@ constexpr int SRC_LDS = 4096;               // doubles of LDS for the table rows
 struct SrcRow {
     int kind;                   // SRC_*; SRC_NONE: the caller's row
     int var;                    // SRC_NONE: the row's place among the caller's rows
-    long long den;              // SINE: f_den; TABLE: P
+    long long den;              // SINE, MULTISINE: f_den; TABLE: P
     const double *amp, *off;    // default 1, 0
     const long long *fnum, *phase;      // default 0, 0
     const double *w;            // TABLE: [P]
+    int tones;                  // MULTISINE: amp, fnum, phase are [tones][n] (tone k of instance i at [k * n + i])
 };
 
 struct SrcArgs {
@@ -60,6 +67,7 @@ struct SrcArgs {
     int nu, nin;
     int vec;                    // 16-byte stores: nu even, or nu = 1 with len and dpitch even; dst 16-byte aligned
     unsigned long long lds_rows;        // the table rows whose windows are staged in LDS
+    int multi;                  // a row is MULTISINE: the launch takes the multi-tone instantiation
 };
 
 struct alignas(16) SrcPair { double a, b; };
@@ -95,8 +103,8 @@ ACME_HD inline void src_stage(const SrcArgs &A, long long by, int tid, double *l
 
 // what a thread keeps of one of its rows: everything that does not depend on the instance ...
 struct SrcSlot {
-    int kind, var;
-    unsigned long long den;     // SINE: f_den; TABLE: the index's modulus (the window's length, or P from HBM)
+    int kind, var, tones;
+    unsigned long long den;     // SINE, MULTISINE: f_den; TABLE: the index's modulus (the window's length, or P from HBM)
     unsigned long long m0;      // SINE: (n0 + first sample) mod f_den; TABLE: the first sample's index
     unsigned long long dstep;   // dt mod den
     const double *amp, *off, *tab;
@@ -108,15 +116,23 @@ struct SrcRun {
     unsigned long long k, step;
     const double *u;            // SRC_NONE: the caller's row at the thread's next sample
 };
+// a MULTISINE row's tones 1 ... SRC_MAX_TONES - 1 beside tone 0 (which lives in amp, k, step above)
+struct SrcRunMulti : SrcRun {
+    double ampx[SRC_MAX_TONES - 1];
+    unsigned long long kx[SRC_MAX_TONES - 1], stepx[SRC_MAX_TONES - 1];
+};
+template <bool MT> struct SrcRunOf { typedef SrcRun type; };
+template <> struct SrcRunOf<true> { typedef SrcRunMulti type; };
 
-// row `row`, first sample tb + ts of the slice, dt samples per step
+// row `row`, first sample tb + ts of the slice, dt samples per step (MT: the launch may hold MULTISINE rows)
+template <bool MT>
 ACME_HD inline void src_slot_init(const SrcArgs &A, int row, long long tb, long long tl, long long ts, long long dt, const double *lds,
                                   SrcSlot &S) {
     const SrcRow &R = A.rows[row];
-    S.kind = R.kind; S.var = R.var;
+    S.kind = R.kind; S.var = R.var; S.tones = R.tones;
     S.amp = R.amp; S.off = R.off; S.fnum = R.fnum; S.phase = R.phase; S.tab = R.w;
     S.den = 1; S.m0 = 0; S.dstep = 0;
-    if (R.kind == SRC_SINE) {
+    if (R.kind == SRC_SINE || (MT && R.kind == SRC_MULTISINE)) {
         S.den = (unsigned long long)R.den;
         S.m0 = ((unsigned long long)(A.n0 % R.den) + (unsigned long long)(tb + ts)) % S.den;      // (n mod f_den first)
         S.dstep = (unsigned long long)dt % S.den;
@@ -146,6 +162,27 @@ ACME_HD inline void src_run_init(const SrcArgs &A, const SrcSlot &S, long long i
     } else if (S.kind == SRC_NONE && A.uv)
         R.u = A.uv + (i * A.upitch + tb + ts) * A.nin + S.var;
 }
+// ... of a launch that may hold MULTISINE rows: per tone the two reductions of a SINE row
+ACME_HD inline void src_run_init(const SrcArgs &A, const SrcSlot &S, long long i, long long tb, long long ts, SrcRunMulti &R) {
+    src_run_init(A, S, i, tb, ts, static_cast<SrcRun &>(R));
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < SRC_MAX_TONES - 1; ++j) { R.ampx[j] = 0.0; R.kx[j] = 0ull; R.stepx[j] = 0ull; }
+    if (S.kind != SRC_MULTISINE) return;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 0; k < SRC_MAX_TONES; ++k) {
+        if (k >= S.tones) continue;         // (constant indices after unrolling: the tones stay in registers)
+        const long long e = k * A.n + i;
+        const unsigned long long f = (unsigned long long)S.fnum[e], p = S.phase ? (unsigned long long)S.phase[e] : 0ull;
+        const unsigned long long kap = (f * S.m0 + p) % S.den, st = (f * S.dstep) % S.den;
+        const double a = S.amp ? S.amp[e] : 1.0;
+        if (k == 0) { R.amp = a; R.k = kap; R.step = st; }
+        else { R.ampx[k - 1] = a; R.kx[k - 1] = kap; R.stepx[k - 1] = st; }
+    }
+}
 
 // the row's value at the thread's current sample; on to the next (dt samples later)
 ACME_HD inline double src_next(const SrcSlot &S, SrcRun &R, long long ustep) {
@@ -163,8 +200,27 @@ ACME_HD inline double src_next(const SrcSlot &S, SrcRun &R, long long ustep) {
     if (R.k >= S.den) R.k -= S.den;
     return v;
 }
+// ... of a launch that may hold MULTISINE rows: the chain over the row's tones
+ACME_HD inline double src_next(const SrcSlot &S, SrcRunMulti &R, long long ustep) {
+    if (S.kind != SRC_MULTISINE) return src_next(S, static_cast<SrcRun &>(R), ustep);
+    double v = fma(R.amp, sin(phase_angle((long long)R.k, (long long)S.den)), R.off);
+    R.k += R.step;
+    if (R.k >= S.den) R.k -= S.den;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < SRC_MAX_TONES - 1; ++j) {
+        if (j + 1 < S.tones) {
+            v = fma(R.ampx[j], sin(phase_angle((long long)R.kx[j], (long long)S.den)), v);
+            R.kx[j] += R.stepx[j];
+            if (R.kx[j] >= S.den) R.kx[j] -= S.den;
+        }
+    }
+    return v;
+}
 
 // thread tid of block (bx, by): instances bx SRC_INST ..., samples by SRC_TILE ...
+template <bool MT>
 ACME_HD inline void src_thread(const SrcArgs &A, long long bx, long long by, int tid, const double *lds) {
     const int nu = A.nu;
     const long long tb = by * SRC_TILE, tl = A.len - tb < SRC_TILE ? A.len - tb : SRC_TILE;
@@ -182,11 +238,12 @@ ACME_HD inline void src_thread(const SrcArgs &A, long long bx, long long by, int
         dt = act / per;
     }
     SrcSlot s0, s1;
-    src_slot_init(A, r0, tb, tl, ts, dt, lds, s0);
-    if (A.vec) src_slot_init(A, r1, tb, tl, ts1, dt, lds, s1);
+    if (MT) s1 = SrcSlot{};         // (read by src_run_init's tone loop only when A.vec has filled it)
+    src_slot_init<MT>(A, r0, tb, tl, ts, dt, lds, s0);
+    if (A.vec) src_slot_init<MT>(A, r1, tb, tl, ts1, dt, lds, s1);
     const long long ustep = dt * A.nin;
     for (long long i = bx * SRC_INST; i < (bx + 1) * SRC_INST && i < A.n; ++i) {
-        SrcRun q0, q1;
+        typename SrcRunOf<MT>::type q0, q1;
         src_run_init(A, s0, i, tb, ts, q0);
         double *d = A.dst + (i * A.dpitch + tb) * nu;
         if (A.vec) {
@@ -202,11 +259,14 @@ ACME_HD inline void src_thread(const SrcArgs &A, long long bx, long long by, int
 }
 
 // the launch's shape: which table rows are staged in LDS (in row order while their windows fit; use_lds false: none) and
-// whether 16-byte stores are possible
+// whether 16-byte stores are possible; which instantiation runs
 inline void src_plan(SrcArgs &A, const SrcRow *host_rows, bool use_lds) {
     const long long tmax = A.len < SRC_TILE ? A.len : SRC_TILE;
     long long used = 0;
     A.lds_rows = 0ull;
+    A.multi = 0;
+    for (int r = 0; r < A.nu; ++r)
+        if (host_rows[r].kind == SRC_MULTISINE) A.multi = 1;
     for (int r = 0; r < A.nu && use_lds; ++r) {
         if (host_rows[r].kind != SRC_TABLE) continue;
         const long long win = host_rows[r].den < tmax ? host_rows[r].den : tmax;
@@ -235,7 +295,15 @@ __global__ __launch_bounds__(acme::SRC_BLOCK) void acme_source_kernel(acme::SrcA
         acme::src_stage(A, blockIdx.y, threadIdx.x, lds);
         __syncthreads();
     }
-    acme::src_thread(A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+    acme::src_thread<false>(A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+__global__ __launch_bounds__(acme::SRC_BLOCK) void acme_source_multi_kernel(acme::SrcArgs A) {
+    __shared__ double lds[acme::SRC_LDS];
+    if (A.lds_rows) {           // (uniform over the launch)
+        acme::src_stage(A, blockIdx.y, threadIdx.x, lds);
+        __syncthreads();
+    }
+    acme::src_thread<true>(A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
 }
 __global__ __launch_bounds__(256) void acme_source_copy_kernel(acme::SrcCopyArgs A) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -244,7 +312,8 @@ __global__ __launch_bounds__(256) void acme_source_copy_kernel(acme::SrcCopyArgs
 namespace acme {
 inline int src_launch(const SrcArgs &A, hipStream_t st) {
     const dim3 grid((unsigned)((A.n + SRC_INST - 1) / SRC_INST), (unsigned)((A.len + SRC_TILE - 1) / SRC_TILE));
-    hipLaunchKernelGGL(acme_source_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
+    if (A.multi) hipLaunchKernelGGL(acme_source_multi_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
+    else hipLaunchKernelGGL(acme_source_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
     return (int)hipGetLastError();
 }
 inline int src_launch_copy(const SrcCopyArgs &A, hipStream_t st) {
@@ -259,7 +328,10 @@ inline int src_launch(const SrcArgs &A, void *) {
     for (long long by = 0; by * SRC_TILE < A.len; ++by) {
         for (int tid = 0; tid < SRC_BLOCK && A.lds_rows; ++tid) src_stage(A, by, tid, lds.data());
         for (long long bx = 0; bx * SRC_INST < A.n; ++bx)
-            for (int tid = 0; tid < SRC_BLOCK; ++tid) src_thread(A, bx, by, tid, lds.data());
+            for (int tid = 0; tid < SRC_BLOCK; ++tid) {
+                if (A.multi) src_thread<true>(A, bx, by, tid, lds.data());
+                else src_thread<false>(A, bx, by, tid, lds.data());
+            }
     }
     return 0;
 }

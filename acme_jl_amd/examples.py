@@ -140,6 +140,27 @@ def level_sweep_thd(model, levels, consts=(), f0=(10, 441), fs=44100, seconds=1,
     return m.thd()[:, 0], m
 
 
+def ccif_sweep_imd(model, centres, levels, spacing=1000, consts=(), fs=44100, seconds=1, settle=1, signal_row=0, device=None):
+    """CCIF / DFD intermodulation against the tone pair's centre frequency over a level grid, in one batch: instance
+    (c, l) is driven by two equal tones at ``centres[c] -+ spacing / 2`` Hz (integers at f_den = ``fs``) of amplitude
+    ``levels[l]`` each -- a multisine source on ``signal_row``, the other rows held at ``consts`` --, and measured at both
+    tones, at f2 - f1, 2 f1 - f2 and 2 f2 - f1 (``ModelRunner.set_measurement_bins``): no u, no y.  Returns
+    (imd [len(centres), len(levels)], Measurement).  Needs a GPU."""
+    import numpy as np
+    from .runner import ModelRunner
+    centres, levels = np.asarray(centres, dtype=np.int64), np.asarray(levels, dtype=np.float64)
+    c, l = (a.ravel() for a in np.meshgrid(centres, levels, indexing="ij"))
+    f_num = np.stack([c - spacing // 2, c - spacing // 2 + spacing])
+    r = ModelRunner(model, len(c), device=device)
+    r.set_source(signal_row, "multisine", f_den=fs, f_num=f_num, amp=np.stack([l, l]))
+    for row, value in dict(consts).items():
+        r.set_source(row, "const", offset=value)
+    r.set_measurement_bins([[1, 0], [0, 1], [-1, 1], [2, -1], [-1, 2]], start=settle * fs, length=seconds * fs, tones_from_source=signal_row)
+    r.measure(T=(settle + seconds) * fs)
+    m = r.measurement()
+    return m.imd([0, 1], [2, 3, 4])[:, 0].reshape(len(centres), len(levels)), m
+
+
 def sallenkey():
     return build([
         ("j_in", voltagesource(), {"-": "gnd"}),

@@ -64,11 +64,13 @@ ABI_SYMBOLS = [
     "acme_batch_set_source_const", "acme_batch_set_source_sine", "acme_batch_set_source_table", "acme_batch_clear_source",
     "acme_batch_set_source_clock", "acme_batch_get_source_clock", "acme_batch_run_sources", "acme_batch_run_sources_async",
     "acme_batch_render_sources",
+    "acme_batch_set_source_multisine", "acme_batch_set_measurement_bins",
 ]
 
-SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE = 1, 2, 3
-_SOURCE_KINDS = {"const": SOURCE_CONST, "sine": SOURCE_SINE, "table": SOURCE_TABLE,
-                 SOURCE_CONST: SOURCE_CONST, SOURCE_SINE: SOURCE_SINE, SOURCE_TABLE: SOURCE_TABLE}
+SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE = 1, 2, 3, 4
+MAX_SOURCE_TONES = 4
+_SOURCE_KINDS = {"const": SOURCE_CONST, "sine": SOURCE_SINE, "table": SOURCE_TABLE, "multisine": SOURCE_MULTISINE,
+                 SOURCE_CONST: SOURCE_CONST, SOURCE_SINE: SOURCE_SINE, SOURCE_TABLE: SOURCE_TABLE, SOURCE_MULTISINE: SOURCE_MULTISINE}
 
 
 def _preload_torch_hip_runtime():
@@ -165,6 +167,9 @@ class Library:
         L.acme_batch_run_sources.argtypes = [vp, vp, vp, C.c_longlong, C.c_int, vp]
         L.acme_batch_run_sources_async.argtypes = [vp, vp, vp, C.c_longlong, C.c_int, vp]
         L.acme_batch_render_sources.argtypes = [vp, vp, vp, C.c_longlong, C.c_int, vp]
+        L.acme_batch_set_source_multisine.argtypes = [vp, C.c_int, C.c_longlong, C.c_int, lp, lp, dp, dp]
+        L.acme_batch_set_measurement_bins.argtypes = [vp, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, lp, C.c_int, ip,
+                                                      C.c_ulonglong]
 
     def check(self, rc):
         if rc < 0:
@@ -203,13 +208,28 @@ def design_oversampling_filter(factor, lib=None):
 class Measurement:
     """What ``ModelRunner.measurement()`` returns: per instance and measured output row (``rows``, ascending) the window's
     ``mean``, ``rms``, ``min``, ``max`` and ``peak`` (N, nrows), and ``harmonics`` (N, nrows, H), the complex amplitudes
-    A_h = (2 / count) sum_m y[m] exp(-j h w m) of the fundamental's harmonics h = 1 ... H; ``count`` samples were measured."""
+    A_h = (2 / count) sum_m y[m] exp(-j h w m) of the fundamental's harmonics h = 1 ... H; ``count`` samples were measured.
+    After ``set_measurement_bins`` the same array is the bins' complex amplitudes A_b (N, nrows, B), also as ``bins``."""
 
     def __init__(self, out, count, rows):
         self.count = int(count)
         self.rows = tuple(rows)
         self.mean, self.rms, self.min, self.max = (out[:, :, k].copy() for k in range(4))
         self.harmonics = out[:, :, 4::2] + 1j * out[:, :, 5::2]
+
+    @property
+    def bins(self):
+        """the complex amplitudes of a bins measurement (N, nrows, B), in the order of ``coef``"""
+        return self.harmonics
+
+    def imd(self, fundamental_bins, product_bins):
+        """intermodulation distortion (N, nrows): the root-sum-square of the amplitudes of the bins ``product_bins`` over
+        that of the bins ``fundamental_bins`` (indices into ``bins``)"""
+        a = np.abs(self.harmonics)
+        fb, pb = list(fundamental_bins), list(product_bins)
+        if not fb or not pb:
+            raise ValueError("IMD needs at least one fundamental bin and one product bin")
+        return np.sqrt((a[:, :, pb] ** 2).sum(axis=2)) / np.sqrt((a[:, :, fb] ** 2).sum(axis=2))
 
     @property
     def peak(self):
@@ -438,8 +458,41 @@ class ModelRunner:
         self._meas = (int(harmonics), rows)
         return self
 
+    def set_measurement_bins(self, coef, start=0, length=0, rows=None, f_den=None, f_num=None, tones_from_source=None):
+        """Arm a measurement whose bins are integer combinations of per-instance tones
+        (``acme_batch_set_measurement_bins``): ``coef`` (B, tones) integers, bin b of instance i at
+        (sum_j coef[b][j] f_num[j][i]) mod f_den of ``f_den`` -- the sum and difference products of a two-tone test.
+        ``f_num``: (tones, N) or (tones,) integers; or ``tones_from_source=row``: ``f_den`` and the tones of the multisine (or
+        sine) source armed on input row ``row``.  ``measurement().bins`` then holds the complex amplitudes (N, nrows, B); a
+        combination below zero reads the mirrored line (the conjugate amplitude): prefer signs that give a positive frequency."""
+        if tones_from_source is not None:
+            if f_num is not None or f_den is not None:
+                raise ValueError("tones_from_source excludes f_den / f_num")
+            if self._sources.get(int(tones_from_source)) not in (SOURCE_SINE, SOURCE_MULTISINE):
+                raise ValueError(f"input row {tones_from_source} has no multisine or sine source to take the tones from")
+            f_den, f_num = self._sine[int(tones_from_source)]
+            f_num = np.atleast_2d(np.broadcast_to(f_num, (self.n,)) if np.ndim(f_num) < 2 else f_num)
+        if f_num is None or f_den is None:
+            raise ValueError("bins need f_den and f_num, or tones_from_source")
+        fa, fp, tones = self._per_tone(f_num, np.int64, "f_num")
+        ca = np.asarray(coef)
+        if ca.size == 0:
+            ca = np.zeros((0, tones), dtype=np.int32)
+        if ca.ndim == 1 and tones == 1:
+            ca = ca[:, None]
+        if ca.ndim != 2 or ca.shape[1] != tones or not np.all(ca == np.round(ca)):
+            raise DimensionMismatch(f"coef must be (bins, {tones}) integers")
+        if np.abs(ca).max(initial=0) > 32767:
+            raise ValueError("coef: |coefficient| <= 32767")
+        ca = np.ascontiguousarray(ca, dtype=np.int32)
+        spec, rows = measure_spec(self.model.ny, start, length, (0, int(f_den)), 0, rows)
+        self.lib.check(self.lib.L.acme_batch_set_measurement_bins(self.h, spec[0], spec[1], int(f_den), tones, fp, ca.shape[0],
+                                                                  _ip(ca), spec[5]))
+        self._meas = (ca.shape[0], rows)
+        return self
+
     def measurement_plan(self):
-        """The plan of the armed per-instance measurement (``acme_batch_get_measurement_plan``): a dict with ``groups``
+        """The plan of the armed per-instance or bins measurement (``acme_batch_get_measurement_plan``): a dict with ``groups``
         (distinct f_num), ``chunk`` (samples per step), ``perm`` (lane slot -> pair) and ``wave_group`` (per wave of 64
         slots its one group -- the broadcast loop --, or -1: a mixed wave of per-lane loads)."""
         if self._meas is None:
@@ -511,6 +564,23 @@ class ModelRunner:
             raise DimensionMismatch(f"{what} must be integers")
         return arr, arr.ctypes.data_as(C.POINTER(C.c_double if dtype is np.float64 else C.c_longlong))
 
+    def _per_tone(self, a, dtype, what, tones=None):
+        """a per-tone, per-instance parameter -- (tones, N), (tones,) (one value per tone for every instance) or, with
+        ``tones`` known, a scalar -- as the ABI takes it: (array kept alive, pointer, tones); None stays None"""
+        if a is None:
+            return None, None, tones
+        src = np.asarray(a)
+        if src.ndim == 0 and tones is not None:
+            src = np.full((tones,), src)
+        if src.ndim == 1:
+            src = src[:, None]
+        if src.ndim != 2 or src.shape[1] not in (1, self.n) or (tones is not None and src.shape[0] != tones):
+            raise DimensionMismatch(f"{what} must have shape (tones, {self.n}) or (tones,)")
+        arr = np.ascontiguousarray(np.broadcast_to(src.astype(dtype), (src.shape[0], self.n)))
+        if dtype is np.int64 and not np.all(arr == src):
+            raise DimensionMismatch(f"{what} must be integers")
+        return arr, arr.ctypes.data_as(C.POINTER(C.c_double if dtype is np.float64 else C.c_longlong)), src.shape[0]
+
     def set_source(self, row, kind, amp=None, offset=None, f_den=None, f_num=None, phase=None, table=None):
         """Give input row ``row`` a source (``acme_batch_set_source_*``): the library generates the row on the device, at
         source clock n (base-rate samples since the first source was armed) for instance i
@@ -519,15 +589,30 @@ class ModelRunner:
         * ``"sine"``: ``fma(amp[i], sin(2 pi kappa / f_den), offset[i])``, kappa = (f_num[i] n + phase[i]) mod f_den -- the
           frequency f_num[i] / f_den of the sample rate per instance, the phase reduced exactly in integers
         * ``"table"``: ``fma(amp[i], table[n mod P], offset[i])``, a looped wavetable of P entries
+        * ``"multisine"``: a sum of 1 ... 4 sines, one fma chain in tone order from ``offset[i]``; ``f_num`` (required),
+          ``phase``, ``amp``: (tones, N) or (tones,) -- per-instance tone frequencies, levels and relative phases (a two-tone
+          intermodulation test); one tone is the ``"sine"`` row bit for bit
 
         ``amp``, ``offset``, ``f_num``, ``phase``: None (amp 1, the others 0), a scalar or N values.  ``run_sources`` then runs
         without these rows; its results are those of ``run`` on ``render_sources``' array, bit for bit."""
         k = _SOURCE_KINDS.get(kind)
         if k is None:
-            raise ValueError(f"unknown source kind {kind!r}: 'const', 'sine' or 'table'")
-        aa, ap = self._per_instance(amp, np.float64, "amp")
+            raise ValueError(f"unknown source kind {kind!r}: 'const', 'sine', 'multisine' or 'table'")
         oa, op = self._per_instance(offset, np.float64, "offset")
         L = self.lib.L
+        if k == SOURCE_MULTISINE:
+            if f_den is None or f_num is None:
+                raise ValueError("a multisine source needs f_den and f_num")
+            fa, fp, tones = self._per_tone(f_num, np.int64, "f_num")
+            if not 1 <= tones <= MAX_SOURCE_TONES:
+                raise ValueError(f"a multisine source has 1 ... {MAX_SOURCE_TONES} tones")
+            pa, pp, _ = self._per_tone(phase, np.int64, "phase", tones)
+            aa, ap, _ = self._per_tone(amp, np.float64, "amp", tones)
+            self.lib.check(L.acme_batch_set_source_multisine(self.h, int(row), int(f_den), tones, fp, pp, ap, op))
+            self._sine[int(row)] = (int(f_den), fa.copy())
+            self._sources[int(row)] = k
+            return self
+        aa, ap = self._per_instance(amp, np.float64, "amp")
         if k == SOURCE_CONST:
             self.lib.check(L.acme_batch_set_source_const(self.h, int(row), op))
         elif k == SOURCE_SINE:
@@ -1011,6 +1096,16 @@ class MultiDeviceRunner:
                 r.set_measurement(start, length, f0, harmonics, rows, f_den, part, f0_from_source)
         return self
 
+    def set_measurement_bins(self, coef, start=0, length=0, rows=None, f_den=None, f_num=None, tones_from_source=None):
+        """``ModelRunner.set_measurement_bins`` on every device's batch, per-instance ``f_num`` (tones, N) sliced over the devices"""
+        if f_num is not None and np.ndim(f_num) == 2 and np.shape(f_num)[1] not in (1, self.n):
+            raise DimensionMismatch(f"per-instance tones need (tones, {self.n}) values")
+        for r, (lo, hi) in zip(self.runners, self.ranges):
+            if r is not None:
+                part = f_num if f_num is None or np.ndim(f_num) < 2 or np.shape(f_num)[1] == 1 else np.asarray(f_num)[:, lo:hi]
+                r.set_measurement_bins(coef, start, length, rows, f_den, part, tones_from_source)
+        return self
+
     def reset_measurement(self):
         for r in self.runners:
             if r is not None:
@@ -1031,10 +1126,19 @@ class MultiDeviceRunner:
     # ---- sources: the per-instance parameters sliced over the devices ---------------------------
     def set_source(self, row, kind, amp=None, offset=None, f_den=None, f_num=None, phase=None, table=None):
         """``ModelRunner.set_source`` on every device's batch, each with its instances' parameters"""
+        multi = _SOURCE_KINDS.get(kind) == SOURCE_MULTISINE
+
         def part(a, lo, hi):
+            if multi and a is not None and np.ndim(a) == 2 and a is not offset:
+                return a if np.shape(a)[1] == 1 else np.asarray(a)[:, lo:hi]
+            if multi and a is not offset:
+                return a                    # ((tones,): one value per tone for every instance)
             return a if a is None or np.ndim(a) == 0 else np.asarray(a)[lo:hi]
         for a in (amp, offset, f_num, phase):
-            if a is not None and np.ndim(a) != 0 and len(a) != self.n:
+            if multi and a is not offset:
+                if a is not None and np.ndim(a) == 2 and np.shape(a)[1] not in (1, self.n):
+                    raise DimensionMismatch(f"per-instance tone parameters need (tones, {self.n}) values")
+            elif a is not None and np.ndim(a) != 0 and len(a) != self.n:
                 raise DimensionMismatch(f"per-instance source parameters need {self.n} values")
         for r, (lo, hi) in zip(self.runners, self.ranges):
             if r is not None:

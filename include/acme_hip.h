@@ -283,10 +283,35 @@ int acme_batch_set_measurement(acme_batch *b, long long start, long long length,
 int acme_batch_set_measurement_per_instance(acme_batch *b, long long start, long long length, long long f_den,
                                             long long *f_num /* host, [N], only read */, int harmonics,
                                             unsigned long long rows);
-/* the plan of the armed per-instance measurement (tests, probes; any pointer may be NULL): *n_groups distinct f_num, *chunk
- * samples per step, perm[N nrows]: lane slot -> pair (i nrows + j), wave_group[(N nrows + 63) / 64]: the one group of the 64
+/* the plan of the armed per-instance or bins measurement (tests, probes; any pointer may be NULL): *n_groups distinct f_num, *chunk
+ * samples per step (bins: *n_groups distinct tone tuples), perm[N nrows]: lane slot -> pair (i nrows + j), wave_group[(N nrows + 63) / 64]: the one group of the 64
  * slots' wave (the broadcast loop), or -1 (mixed: per-lane loads).  ACME_ERR_INVALID while no such measurement is armed. */
 int acme_batch_get_measurement_plan(acme_batch *b, long long *n_groups, long long *chunk, long long *perm, int *wave_group);
+/* arm a measurement whose BINS are integer combinations of per-instance tones: an intermodulation test (CCIF / DFD: 19 kHz +
+ * 20 kHz read at f2 - f1, 2 f1 - f2, 2 f2 - f1; SMPTE: 60 Hz + 7 kHz read at f2 +- n f1) driven by a MULTISINE source (below) is
+ * measured in the same batch.  The semantics of acme_batch_set_measurement with the harmonics h f_num replaced by the bins
+ *   k[b][i] = (sum_j coef[b][j] f_num[j][i]) mod f_den    b = 0 ... bins - 1, the non-negative residue, exact 64-bit integers
+ *   th = 2 pi ((k[b][i] (m mod f_den)) mod f_den) / f_den, C_b and S_b each ONE fma chain in sample order
+ *   tones, f_num    1 ... ACME_MAX_SOURCE_TONES tones; f_num: a HOST array [tones][N] (tone j of instance i at f_num[j * N + i]),
+ *                   0 <= f_num < f_den < 2^31, copied by the call (only read)
+ *   bins, coef      0 ... ACME_MAX_HARMONICS bins; coef: a host array [bins][tones], |coef| <= 32767 (the sum stays below 2^48)
+ * acme_batch_get_measurement writes out[N][nrows][4 + 2 bins]: the four moments (the same chains as ever), then Re and Im of
+ * A_b = (2 / count) (C_b - j S_b).  Bin b of instance i is, bit for bit, harmonic 1 of acme_batch_set_measurement(f_num =
+ * k[b][i], f_den, harmonics = 1) on an identical run; with tones = 1 and coef[b] = b + 1 the whole result is that of
+ * acme_batch_set_measurement_per_instance with harmonics = bins.
+ * NEGATIVE COMBINATIONS: a combination below zero is reduced into 0 ... f_den - 1 like any other: f2 - f1 with f1 > f2 becomes
+ * f_den - (f1 - f2) -- the same spectral line of a real signal read at its mirror frequency, so |A_b| is the line's amplitude
+ * and Im A_b comes out NEGATED (A_b is the conjugate of the amplitude at f1 - f2).  Choose the signs so that every bin is a
+ * positive frequency (f1 - f2 here) when phases matter.  A bin with k = 0 reads C = the sum and S = 0 exactly.
+ * The instances are grouped by distinct tone tuple (f_num[0][i], ...), in lexicographic order; plan, table budget, chunk rule,
+ * ACME_MEAS_TABLE_BUDGET and acme_batch_get_measurement_plan are those of the per-instance form, and so are _reset_measurement
+ * (the bins stay), _clear_measurement, acme_batch_set_matrices and the refusal with acme_batch_set_isolation.  Arming any of
+ * the three forms replaces the others.  Validates as the per-instance form does (ACME_ERR_INVALID: tones or bins out of range,
+ * null f_num, null coef with bins > 0, an f_num out of range -- named by tone and instance --, a coefficient out of range).
+ * WHICH WINDOW: length = f_den samples hold whole periods of every tone and every product. */
+int acme_batch_set_measurement_bins(acme_batch *b, long long start, long long length, long long f_den, int tones,
+                                    long long *f_num /* host, [tones][N], only read */, int bins,
+                                    const int *coef /* host, [bins][tones] */, unsigned long long rows);
 /* switch the measurement off (y = NULL is refused again) */
 int acme_batch_clear_measurement(acme_batch *b);
 /* zero the accumulators and restart the window's clock (the armed parameters stay) */
@@ -310,6 +335,12 @@ int acme_batch_get_measurement(acme_batch *b, double *out, long long *count);
  *                         frequency is f_num_i / f_den x the base sample rate per instance: a frequency sweep is one batch
  *     ACME_SOURCE_TABLE   fma(amp_i, w[n mod P], offset_i): a looped wavetable w[P], 1 <= P <= ACME_MAX_SOURCE_TABLE (a chirp,
  *                         a multitone, a recorded bar: P = its length)
+ *     ACME_SOURCE_MULTISINE  a sum of `tones` (1 ... ACME_MAX_SOURCE_TONES) sines, ONE chain in tone order: v = offset_i, then
+ *                         v = fma(amp_ki, sin(th_k), v) for k = 0 ... tones - 1, th_k = 2 pi kappa_k / f_den with
+ *                         kappa_k = (f_num_ki n + phase_ki) mod f_den reduced and rounded exactly as SINE's.  One tone is the
+ *                         SINE row bit for bit.  Per-instance tone frequencies, levels and relative phases: a two-tone
+ *                         intermodulation sweep (the pair's centre, spacing, ratio) is one batch.  The per-tone arrays are
+ *                         [tones][N]: tone k of instance i at [k * N + i]
  *   parameters    amp, offset, f_num, phase: HOST arrays of N entries, copied to the device by the call (parameters, not
  *                 signals); NULL = the same default for every instance (amp 1, the others 0).  w: a host array of P entries.
  *                 (f_num and phase are only read.)
@@ -328,7 +359,9 @@ int acme_batch_get_measurement(acme_batch *b, double *out, long long *count);
 #define ACME_SOURCE_CONST 1
 #define ACME_SOURCE_SINE 2
 #define ACME_SOURCE_TABLE 3
+#define ACME_SOURCE_MULTISINE 4
 #define ACME_MAX_SOURCE_TABLE 16777216
+#define ACME_MAX_SOURCE_TONES 4
 /* give input row `row` a source (replacing the one it has).  Validates its arguments (ACME_ERR_INVALID: row beyond the model's
  * inputs, f_den or P out of range, an f_num_i or phase_i outside 0 ... f_den - 1, non-finite amp / offset).  Completes the
  * batch's outstanding work first. */
@@ -337,6 +370,10 @@ int acme_batch_set_source_sine(acme_batch *b, int row, long long f_den, long lon
                                const double *amp, const double *offset);
 int acme_batch_set_source_table(acme_batch *b, int row, const double *w, long long P, const double *amp,
                                 const double *offset);
+/* f_num (required), phase, amp: [tones][N]; offset: [N].  ACME_ERR_INVALID also for tones outside 1 ... ACME_MAX_SOURCE_TONES
+ * and a null f_num; an f_num or phase out of range is named by tone and instance. */
+int acme_batch_set_source_multisine(acme_batch *b, int row, long long f_den, int tones, long long *f_num, long long *phase,
+                                    const double *amp, const double *offset);
 /* the row is the caller's again; row < 0: every row.  With the last source the clock goes (the next first source starts
  * it at 0). */
 int acme_batch_clear_source(acme_batch *b, int row);

@@ -36,7 +36,8 @@ import ACME: run!, solve, hasconverged, needediterations, set_resabstol!,
 
 export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host_buffers!, release_host_buffers!, set_isolation!, set_balance!,
        MeasureSpec, Measurement, set_measurement!, clear_measurement!, reset_measurement!, measurement, measurement_plan, measure!,
-       set_source!, clear_source!, source_clock, source_clock!, run_sources!, render_sources
+       set_source!, clear_source!, source_clock, source_clock!, run_sources!, render_sources,
+       set_source_multisine!, set_measurement_bins!
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
 
@@ -48,8 +49,9 @@ const ACME_SOLVER_SIMPLE, ACME_SOLVER_HOMOTOPY, ACME_SOLVER_CACHING_HOMOTOPY = C
 const ACME_MEM_HOST, ACME_MEM_DEVICE = Cint(0), Cint(1)
 const ACME_MAX_OVERSAMPLING = 16
 const ACME_MAX_HARMONICS = 32
-const ACME_SOURCE_CONST, ACME_SOURCE_SINE, ACME_SOURCE_TABLE = Cint(1), Cint(2), Cint(3)
+const ACME_SOURCE_CONST, ACME_SOURCE_SINE, ACME_SOURCE_TABLE, ACME_SOURCE_MULTISINE = Cint(1), Cint(2), Cint(3), Cint(4)
 const ACME_MAX_SOURCE_TABLE = 16777216
+const ACME_MAX_SOURCE_TONES = 4
 const KIND_NQ = Dict(1 => 2, 2 => 4, 3 => 5, 4 => 3, 5 => 2, 6 => 4)
 const KIND_NN = Dict(1 => 1, 2 => 2, 3 => 2, 4 => 1, 5 => 1, 6 => 1)
 
@@ -498,6 +500,29 @@ function set_measurement!(r::BatchRunner, spec::MeasureSpec, f_den::Int64, f_num
 end
 
 """
+    set_measurement_bins!(runner, coef::Matrix{<:Integer}, f_den, f_num::Matrix{Int64}; start=0, length=0, rows=())
+
+Arm a measurement whose bins are integer combinations of per-instance tones (`acme_batch_set_measurement_bins`): `f_num` is
+N x tones (column j: tone j of every instance), `coef` is tones x bins (column b: the coefficients of bin b), and bin `b` of
+instance `i` correlates with `(sum_j coef[j, b] f_num[i, j]) mod f_den` of `f_den` -- the sum and difference products of a
+two-tone intermodulation test.  `measurement(runner).harmonics[b, row, i]` is then the complex amplitude of bin `b`.  A
+combination below zero reads the mirrored line (the conjugate amplitude): choose signs that give a positive frequency.
+"""
+function set_measurement_bins!(r::BatchRunner, coef::Matrix{<:Integer}, f_den::Integer, f_num::Matrix{Int64};
+                               start::Integer=0, length::Integer=0, rows=())
+    tones, bins = size(coef)
+    size(f_num) == (r.n, tones) || throw(DimensionMismatch("f_num must be N x tones ($(r.n) x $tones)"))
+    1 <= tones <= ACME_MAX_SOURCE_TONES || error("1 ... $ACME_MAX_SOURCE_TONES tones")
+    spec = MeasureSpec(; start=start, length=length, f0=0 // Int(f_den), harmonics=bins, rows=rows)
+    c = convert(Matrix{Cint}, coef)         # (column-major tones x bins = the ABI's [bins][tones])
+    GC.@preserve f_num c check(ccall((:acme_batch_set_measurement_bins, lib), Cint,
+                (Ptr{Cvoid}, Clonglong, Clonglong, Clonglong, Cint, Ptr{Clonglong}, Cint, Ptr{Cint}, Culonglong),
+                r.h, spec.start, spec.length, f_den, tones, f_num, bins, c, spec.rows))
+    r.meas = spec
+    return r
+end
+
+"""
     measurement_plan(runner) -> (groups, chunk, perm, wave_group)
 
 The plan of the armed per-instance measurement (`acme_batch_get_measurement_plan`): distinct frequencies, samples per
@@ -596,6 +621,29 @@ function set_source!(r::BatchRunner, row::Integer, kind::Symbol; f_den::Integer=
     else
         error("unknown source kind $kind: :const, :sine or :table")
     end
+    push!(r.sources, Int(row))
+    return r
+end
+
+"""
+    set_source_multisine!(runner, row, f_den, f_num::Matrix{Int64}; phase=nothing, amp=nothing, offset=nothing)
+
+Give input row `row` (1-based) a sum of 1 ... 4 sines (`acme_batch_set_source_multisine`): `f_num`, `phase` (`Matrix{Int64}`)
+and `amp` (`Matrix{Float64}`) are N x tones (column k: tone k of every instance), `offset` as for `set_source!`.  The row's
+value is one fma chain in tone order from `offset[i]`; one tone is the `:sine` row bit for bit.
+"""
+function set_source_multisine!(r::BatchRunner, row::Integer, f_den::Integer, f_num::Matrix{Int64};
+                               phase::Union{Nothing,Matrix{Int64}}=nothing, amp::Union{Nothing,Matrix{Float64}}=nothing, offset=nothing)
+    tones = size(f_num, 2)
+    size(f_num, 1) == r.n || throw(DimensionMismatch("f_num must be N x tones"))
+    (phase === nothing || size(phase) == size(f_num)) && (amp === nothing || size(amp) == size(f_num)) ||
+        throw(DimensionMismatch("phase and amp must have the size of f_num"))
+    p = phase === nothing ? Clonglong[] : vec(phase)
+    a = amp === nothing ? Cdouble[] : vec(amp)
+    o = perinstance(Cdouble, offset, r.n)
+    GC.@preserve f_num p a o check(ccall((:acme_batch_set_source_multisine, lib), Cint,
+                (Ptr{Cvoid}, Cint, Clonglong, Cint, Ptr{Clonglong}, Ptr{Clonglong}, Ptr{Cdouble}, Ptr{Cdouble}),
+                r.h, row - 1, f_den, tones, f_num, ptr_or_null(p), ptr_or_null(a), ptr_or_null(o)))
     push!(r.sources, Int(row))
     return r
 end
