@@ -159,6 +159,8 @@ struct acme_batch {
         // bins (acme_batch_set_measurement_bins): the per-instance plan over groups of distinct tone tuples, H = the bins
         bool bins = false;
         long long *d_kbin_g = nullptr;           // [F][H]: the groups' reduced bin frequencies
+        // series (acme_batch_set_measurement_series): W windows of win samples, one every hop; d_acc is [W][4 + 2H][N nrows]
+        long long win = 0, hop = 0, W = 0;       // W = 0: one window, [start, start + length)
     } meas;
     // Input rows generated on the device (acme_batch_set_source_*, acme_source.h): the rows' descriptions and per-instance
     // parameters in device memory, the source clock
@@ -1291,12 +1293,19 @@ static int os_grow(double **p, size_t *cap, size_t bytes) {
 // the meas.pos samples since arming: the part inside the window [start, start + length), chunk by chunk
 static int meas_step(acme_batch *b, const double *y, long long n, long long pitch, be::stream_t st) {
     acme_batch::Measurement &M = b->meas;
-    const long long end = M.length ? M.start + M.length : LLONG_MAX;
+    const long long end = M.W ? M.start + (M.W - 1) * M.hop + M.win : M.length ? M.start + M.length : LLONG_MAX;
     const long long lo = M.pos > M.start ? M.pos : M.start, hi = M.pos + n < end ? M.pos + n : end;
     for (long long s = lo; M.nrows > 0 && s < hi; s += M.chunk) {
         const long long len = hi - s < M.chunk ? hi - s : M.chunk;
         MeasArgs A{y, M.d_acc, M.d_tw, b->N, len, pitch, s - M.pos, b->P.actual.ny, M.nrows, M.H, {}};
         memcpy(A.row, M.row, sizeof(A.row));
+        if (M.W) {      // a series: the chunk's table and ONE kernel, whatever windows the chunk holds
+            const MeasSeries S{M.win, M.hop, M.W, s - M.start};
+            const MeasSeriesTwArgs W{M.d_tw, M.bins ? M.d_kbin_g : M.pi ? M.d_fnum_g : nullptr, M.f_num, M.f_den, len, S, M.H,
+                                     M.pi ? M.F : 1, M.bins ? 1 : 0};
+            HIPCHK(meas_series_launch(W, MeasSeriesArgs{MeasPiArgs{A, M.d_perm, M.d_sgrp, M.d_wgrp}, S}, M.pi, st));
+            continue;
+        }
         if (M.bins) {
             const MeasBinsTwArgs W{M.d_tw, M.d_kbin_g, s - M.start, len, M.f_den, M.H, M.F};
             HIPCHK(meas_bins_launch(W, MeasPiArgs{A, M.d_perm, M.d_sgrp, M.d_wgrp}, st));
@@ -2117,11 +2126,15 @@ int acme_batch_set_oversampling(acme_batch *b, int factor, const double *h_up, i
 // the accumulators' start values and the window's start (acme_batch_set_measurement / _reset_measurement)
 static int meas_zero(acme_batch *b) {
     acme_batch::Measurement &M = b->meas;
-    const size_t P = (size_t)b->N * M.nrows;
-    std::vector<double> a((size_t)(4 + 2 * M.H) * P);
-    for (int k = 0; k < 4 + 2 * M.H; ++k)
-        for (size_t p = 0; p < P; ++p) a[k * P + p] = meas_init(k);
-    if (!a.empty()) HIPCHK(be::copy_h2d(M.d_acc, a.data(), sizeof(double) * a.size()));
+    const size_t P = (size_t)b->N * M.nrows, slot = (size_t)(4 + 2 * M.H) * P;
+    // (a series: every window's slot, several slots a copy -- 32 MiB of start values at most on the host)
+    const size_t W = M.W ? (size_t)M.W : 1, per = slot ? std::max<size_t>(1, std::min(W, ((size_t)4 << 20) / slot)) : 1;
+    std::vector<double> a(per * slot);
+    for (size_t w = 0; w < per; ++w)
+        for (int k = 0; k < 4 + 2 * M.H; ++k)
+            for (size_t p = 0; p < P; ++p) a[w * slot + k * P + p] = meas_init(k);
+    for (size_t w = 0; slot && w < W; w += per)
+        HIPCHK(be::copy_h2d(M.d_acc + w * slot, a.data(), sizeof(double) * slot * std::min(per, W - w)));
     M.pos = 0;
     return ACME_OK;
 }
@@ -2286,6 +2299,69 @@ int acme_batch_get_measurement_plan(acme_batch *b, long long *n_groups, long lon
     return ACME_OK;
 }
 
+int acme_batch_set_measurement_series(acme_batch *b, long long win, long long hop, long long windows) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    acme_batch::Measurement &M = b->meas;
+    if (!M.on) return fail(ACME_ERR_INVALID, "measurement series: no measurement is armed");
+    if (M.length != 0) return fail(ACME_ERR_INVALID, "measurement series: the armed measurement's length must be 0 (the series sets the windows)");
+    if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement series: samples have been fed since arming (arm or reset the measurement first)");
+    if (win < 1) return fail(ACME_ERR_INVALID, "measurement series: win must be >= 1");
+    if (hop < win) return fail(ACME_ERR_INVALID, "measurement series: hop must be >= win");
+    if (windows < 1 || windows > ACME_MAX_SERIES_WINDOWS)
+        return fail(ACME_ERR_INVALID, "measurement series: windows must be 1 ... " + std::to_string((long long)ACME_MAX_SERIES_WINDOWS));
+    // start + (windows - 1) hop + win within 64 bits (windows - 1 < 2^20)
+    if (win > LLONG_MAX - M.start || (windows > 1 && hop > (LLONG_MAX - M.start - win) / (windows - 1)))
+        return fail(ACME_ERR_INVALID, "measurement series: start + (windows - 1) hop + win overflows");
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    const size_t slot = sizeof(double) * (size_t)(4 + 2 * M.H) * (size_t)b->N * (size_t)M.nrows;
+    if (slot && (size_t)windows > SIZE_MAX / slot)
+        return fail(ACME_ERR_INVALID, "measurement series: windows: the accumulators' size overflows");
+    double *acc = nullptr;
+    HIPCHK(be::dmalloc((void **)&acc, slot * (size_t)windows));
+    (void)be::dfree(M.d_acc);
+    M.d_acc = acc;
+    M.win = win;
+    M.hop = hop;
+    M.W = windows;
+    return meas_zero(b);
+}
+
+int acme_batch_get_measurement_series(acme_batch *b, long long first, long long n, double *out, long long *counts) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const acme_batch::Measurement &M = b->meas;
+    if (!M.on || !M.W) return fail(ACME_ERR_INVALID, "no measurement series is set");
+    if (first < 0 || n < 0 || first > M.W || n > M.W - first)
+        return fail(ACME_ERR_INVALID, "measurement series: first, n: windows " + std::to_string(first) + " ... beyond the series' " +
+                                          std::to_string(M.W));
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    const size_t P = (size_t)b->N * M.nrows, K = (size_t)(4 + 2 * M.H);
+    std::vector<double> a(out ? K * P : 0);
+    for (long long w = first; w < first + n; ++w) {
+        const long long seen = M.pos - M.start - w * M.hop;         // (w hop < the series' span: no overflow)
+        const long long c = seen < 0 ? 0 : seen < M.win ? seen : M.win;
+        if (counts) counts[w - first] = c;
+        if (!out || a.empty()) continue;
+        HIPCHK(be::copy_d2h(a.data(), M.d_acc + (size_t)w * K * P, sizeof(double) * a.size()));
+        const double inv = 1.0 / (double)c;            // (no sample measured yet: NaN and infinities)
+        for (size_t p = 0; p < P; ++p) {
+            double *o = out + ((size_t)(w - first) * P + p) * K;
+            o[0] = a[p] * inv;
+            o[1] = std::sqrt(a[P + p] * inv);
+            o[2] = a[2 * P + p];
+            o[3] = a[3 * P + p];
+            for (int h = 0; h < M.H; ++h) {            // A_h = (2 / count) (C_h - j S_h)
+                o[4 + 2 * h] = 2.0 * a[(4 + 2 * h) * P + p] * inv;
+                o[5 + 2 * h] = -2.0 * a[(5 + 2 * h) * P + p] * inv;
+            }
+        }
+    }
+    return ACME_OK;
+}
+
 int acme_batch_clear_measurement(acme_batch *b) { return set_measurement(b, nullptr); }
 
 int acme_batch_reset_measurement(acme_batch *b) {
@@ -2302,6 +2378,7 @@ int acme_batch_get_measurement(acme_batch *b, double *out, long long *count) {
     if (!b || (!out && !count)) return fail(ACME_ERR_INVALID, "null argument");
     const acme_batch::Measurement &M = b->meas;
     if (!M.on) return fail(ACME_ERR_INVALID, "no measurement is armed");
+    if (M.W) return fail(ACME_ERR_INVALID, "the measurement has a series of windows: use acme_batch_get_measurement_series");
     ON_DEVICE(b);
     HIPCHK(be::device_sync());
     const long long end = M.length ? M.start + M.length : LLONG_MAX;

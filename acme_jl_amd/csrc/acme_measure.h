@@ -40,6 +40,17 @@
 // f_den), the very twiddle of the shared form at f_num = k with one harmonic), and the plan, the budget, the chunk rule and
 // acme_meas_pi_kernel with H = B are the per-instance form's, unchanged.
 //
+// SERIES (acme_batch_set_measurement_series): W windows of `win` samples, one every `hop` samples (1 <= win <= hop), all
+// accumulated in the same pass.  With q = n - start the series-relative number of a sample, window w = q / hop holds it when
+// m' = q - w hop < win; the samples of a gap (m' >= win) and those behind the last window belong to none.  Window w is, bit
+// for bit, the single window [start + w hop, start + w hop + win): the twiddle is meas_twiddle(h, m', ...), every accumulator
+// one chain in sample order from meas_init.  The accumulators are [W][4 + 2H][N nrows], slot w the layout above.  A chunk's
+// table holds, at the chunk's sample t, the twiddle of that sample's m' (meas_series_tw; gap samples are neither written
+// nor read), and ONE kernel per chunk (acme_meas_series_kernel<PI>: the block shape, the tiles and the plan of the kernels
+// above) walks, tile by tile, the sub-ranges (window x tile) -- the same for every pair of the grid, hence wave-uniform: a
+// window's first sample starts from meas_init in registers, a window that continues from an earlier chunk loads its slot,
+// and the window's last sample -- or the chunk's -- stores the slot.  A tile that lies wholly in a gap is not staged.
+//
 // The per-element functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with g++).
 #pragma once
@@ -132,6 +143,42 @@ ACME_HD inline void meas_bins_tw(const MeasBinsTwArgs &A, long long idx) {
     meas_twiddle(1, A.m0 + t, A.kbin_g[g * A.B + b], A.f_den, &A.tw[2 * idx], &A.tw[2 * idx + 1]);
 }
 
+// series: the chunk's first sample is number s0 >= 0 of the series (n - start); the chunk lies inside the series' span
+struct MeasSeries {
+    long long win, hop, W, s0;
+};
+
+// the series' table of one chunk, for any of the three forms: [F][H][len] pairs, at sample t the twiddle of m' (F = 1 and
+// fg = NULL: the shared form at f_num; bins: fg = kbin_g [F][H], every bin harmonic 1 of its reduced frequency)
+struct MeasSeriesTwArgs {
+    double *tw;
+    const long long *fg;        // per-instance: [F] f_num; bins: [F][H] reduced bins; shared: NULL
+    long long f_num, f_den, len;
+    MeasSeries S;
+    int H, F, bins;
+};
+
+struct MeasSeriesArgs {
+    MeasPiArgs B;               // (the shared form: the plan's pointers NULL)
+    MeasSeries S;
+};
+
+// window and window-relative number of the series' sample q, in exact 64-bit integers; false: q belongs to no window
+ACME_HD inline bool meas_series_at(const MeasSeries &S, long long q, long long *w, long long *m) {
+    *w = q / S.hop;
+    *m = q - *w * S.hop;
+    return *w < S.W && *m < S.win;
+}
+
+ACME_HD inline void meas_series_tw(const MeasSeriesTwArgs &A, long long idx) {
+    const long long per = A.H * A.len, g = idx / per, r = idx - g * per;
+    const long long h = r / A.len, t = r - h * A.len;
+    long long w, m;
+    if (!meas_series_at(A.S, A.S.s0 + t, &w, &m)) return;
+    if (A.bins) meas_twiddle(1, m, A.fg[g * A.H + h], A.f_den, &A.tw[2 * idx], &A.tw[2 * idx + 1]);
+    else meas_twiddle(h + 1, m, A.fg ? A.fg[g] : A.f_num, A.f_den, &A.tw[2 * idx], &A.tw[2 * idx + 1]);
+}
+
 // NaN sticks: once an accumulator is NaN it stays so
 ACME_HD inline double meas_min(double m, double v) { return (v < m || v != v) ? v : m; }
 ACME_HD inline double meas_max(double m, double v) { return (v > m || v != v) ? v : m; }
@@ -166,6 +213,33 @@ ACME_HD inline void meas_chain(const MeasArgs &A, long long p, int u) {
     }
     acc[(2 + 2 * u) * P] = c;
     acc[(3 + 2 * u) * P] = sn;
+}
+
+// series: one unit of one pair over the chunk (tw: the table row [H][len] of the pair's group), sample after sample into
+// the sample's window; a window's first sample starts from meas_init
+ACME_HD inline void meas_series_chain(const MeasArgs &A, const MeasSeries &S, const double *twg, long long p, int u) {
+    const long long P = A.n * A.nrows;
+    const long long i = p / A.nrows;
+    const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    const double *tw = twg + 2 * (u > 0 ? u - 1 : 0) * A.len;
+    for (long long t = 0; t < A.len; ++t) {
+        long long w, m;
+        if (!meas_series_at(S, S.s0 + t, &w, &m)) continue;
+        double *acc = A.acc + w * (4 + 2 * A.H) * P + p;
+        const double v = yp[t * A.ny];
+        if (u == 0) {
+            if (m == 0) { acc[0] = 0.0; acc[P] = 0.0; acc[2 * P] = INFINITY; acc[3 * P] = -INFINITY; }
+            acc[0] += v;
+            acc[P] = fma(v, v, acc[P]);
+            acc[2 * P] = meas_min(acc[2 * P], v);
+            acc[3 * P] = meas_max(acc[3 * P], v);
+        } else {
+            double *c = acc + (2 + 2 * u) * P, *sn = acc + (3 + 2 * u) * P;
+            if (m == 0) { *c = 0.0; *sn = 0.0; }
+            *c = fma(v, tw[2 * t], *c);
+            *sn = fma(v, tw[2 * t + 1], *sn);
+        }
+    }
 }
 
 // waves per block and blocks along y for H harmonics: H + 1 units, at most MEAS_MAX_WAVES waves a block
@@ -401,6 +475,149 @@ __global__ __launch_bounds__(256) void acme_meas_bins_tw_kernel(acme::MeasBinsTw
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx < (long long)A.F * A.B * A.len) acme::meas_bins_tw(A, idx);
 }
+__global__ __launch_bounds__(256) void acme_meas_series_tw_kernel(acme::MeasSeriesTwArgs A) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx < (long long)A.F * A.H * A.len) acme::meas_series_tw(A, idx);
+}
+
+// series: acme_meas_kernel (PI = false) / acme_meas_pi_kernel (PI = true) over a chunk that several windows share.  (wt, mt):
+// window and window-relative number of the tile's first sample, kept by every wave alike; (w, m) walk the tile's sub-ranges.
+// `open`: the registers hold window w's accumulators (they are stored when the window, or the chunk, ends).
+template <bool PI>
+__global__ __launch_bounds__(1024) void acme_meas_series_kernel(acme::MeasSeriesArgs G) {
+    using namespace acme;
+    const MeasArgs &A = G.B.A;
+    const MeasSeries &S = G.S;
+    __shared__ double tile[64][MEAS_TILE + 1];          // [slot][sample]: column reads by lane hit distinct banks
+    __shared__ long long base[64];                      // a slot's pair: its first element of the chunk in y
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    const long long P = A.n * A.nrows, p0 = (long long)blockIdx.x * 64;
+    const int u = blockIdx.y * nw + wv;
+    const bool mine = u <= A.H && p0 + lane < P;
+    const long long p = p0 + lane < P ? (PI ? G.B.perm[p0 + lane] : p0 + lane) : 0;
+    if (threadIdx.x < 64 && p0 + lane < P) {
+        const long long i = p / A.nrows;
+        base[lane] = (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    }
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+    const int ia = u == 0 ? 0 : 2 + 2 * u;
+    const long long slot = (long long)(4 + 2 * A.H) * P;
+    const int wg = PI ? G.B.wgrp[blockIdx.x] : 0;      // (wave-uniform: one value per block)
+    const int g = !PI ? 0 : wg >= 0 ? wg : mine ? G.B.sgrp[p0 + lane] : 0;
+    const double *tw = A.tw + 2 * ((long long)g * A.H + (u > 0 ? u - 1 : 0)) * A.len;
+    long long wt = S.s0 / S.hop, mt = S.s0 - wt * S.hop;
+    bool open = false;
+    long long wo = 0;                                   // the open window
+    for (long long tb = 0; tb < A.len; tb += MEAS_TILE) {
+        const int nt = (int)(A.len - tb < MEAS_TILE ? A.len - tb : MEAS_TILE);
+        long long w = wt, m = mt;
+        mt += nt;                                       // (the next tile's first sample)
+        if (mt >= S.hop) { const long long d = mt / S.hop; wt += d; mt -= d * S.hop; }
+        // the tile holds a sample of a window: its first sample does, or a later window begins inside it
+        if (!(w < S.W && (m < S.win || (m + nt > S.hop && w + 1 < S.W)))) continue;
+        __syncthreads();                                // (the previous tile has been read by every wave)
+        for (int pp = wv; pp < 64; pp += nw)
+            if (p0 + pp < P && lane < nt) tile[pp][lane] = A.y[base[pp] + (tb + lane) * A.ny];
+        __syncthreads();
+        if (u > A.H) continue;
+        for (int pos = 0; pos < nt && w < S.W;) {
+            if (m >= S.win) {                           // a gap: to the next window's first sample, or the tile's end
+                const long long adv = S.hop - m < nt - pos ? S.hop - m : nt - pos;
+                pos += (int)adv;
+                m += adv;
+                if (m == S.hop) { m = 0; ++w; }
+                continue;
+            }
+            const int seg = (int)(S.win - m < nt - pos ? S.win - m : nt - pos), end = pos + seg;
+            if (!open) {
+                open = true;
+                wo = w;
+                if (m == 0) {                           // the window's first sample: meas_init
+                    a0 = 0.0; a1 = 0.0; a2 = INFINITY; a3 = -INFINITY;
+                } else if (mine) {                      // it continues from an earlier chunk
+                    const double *acc = A.acc + w * slot + p;
+                    a0 = acc[ia * P];
+                    a1 = acc[(ia + 1) * P];
+                    if (u == 0) { a2 = acc[2 * P]; a3 = acc[3 * P]; }
+                }
+            }
+            if (u == 0) {
+                for (int t = pos; t < end; ++t) {
+                    const double v = tile[lane][t];
+                    a0 += v;
+                    a1 = fma(v, v, a1);
+                    a2 = meas_min(a2, v);
+                    a3 = meas_max(a3, v);
+                }
+            } else if (!PI || wg >= 0) {
+                double cl = 0.0, sl = 0.0;             // lane t holds sample tb + t's twiddle (the sub-range's only)
+                if (lane >= pos && lane < end) { cl = tw[2 * (tb + lane)]; sl = tw[2 * (tb + lane) + 1]; }
+                if (seg == MEAS_TILE) {                // (a whole tile: a fixed trip count the compiler unrolls)
+#pragma unroll 8
+                    for (int t = 0; t < MEAS_TILE; ++t) {
+                        const double v = tile[lane][t];
+                        a0 = fma(v, acme_meas_bcast(cl, t), a0);
+                        a1 = fma(v, acme_meas_bcast(sl, t), a1);
+                    }
+                } else {
+                    for (int t = pos; t < end; ++t) {
+                        const double v = tile[lane][t];
+                        a0 = fma(v, acme_meas_bcast(cl, t), a0);
+                        a1 = fma(v, acme_meas_bcast(sl, t), a1);
+                    }
+                }
+            } else if (mine) {
+                const double2 *tl = reinterpret_cast<const double2 *>(tw) + tb;    // (16-byte aligned: pairs of a hipMalloc'ed table)
+                if (seg == MEAS_TILE) {
+                    double2 nx[8];
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) nx[k] = tl[k];
+#pragma unroll
+                    for (int t = 0; t < MEAS_TILE; t += 8) {
+                        double2 cs[8];
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) cs[k] = nx[k];
+                        if (t + 8 < MEAS_TILE) {       // the next eight samples' loads are in flight under this chain
+#pragma unroll
+                            for (int k = 0; k < 8; ++k) nx[k] = tl[t + 8 + k];
+                        }
+#pragma unroll
+                        for (int k = 0; k < 8; ++k) {
+                            const double v = tile[lane][t + k];
+                            a0 = fma(v, cs[k].x, a0);
+                            a1 = fma(v, cs[k].y, a1);
+                        }
+                    }
+                } else {
+                    for (int t = pos; t < end; ++t) {
+                        const double2 cs = tl[t];
+                        const double v = tile[lane][t];
+                        a0 = fma(v, cs.x, a0);
+                        a1 = fma(v, cs.y, a1);
+                    }
+                }
+            }
+            pos = end;
+            m += seg;
+            if (m == S.win) {                           // the window's last sample: its slot, coalesced along the pairs
+                if (mine) {
+                    double *acc = A.acc + w * slot + p;
+                    acc[ia * P] = a0;
+                    acc[(ia + 1) * P] = a1;
+                    if (u == 0) { acc[2 * P] = a2; acc[3 * P] = a3; }
+                }
+                open = false;
+                if (m == S.hop) { m = 0; ++w; }
+            }
+        }
+    }
+    if (open && mine) {                                 // the chunk ends inside the window
+        double *acc = A.acc + wo * slot + p;
+        acc[ia * P] = a0;
+        acc[(ia + 1) * P] = a1;
+        if (u == 0) { acc[2 * P] = a2; acc[3 * P] = a3; }
+    }
+}
 namespace acme {
 inline int meas_launch(const MeasTwArgs &T, const MeasArgs &A, hipStream_t st) {
     if (A.H > 0) {
@@ -444,6 +661,23 @@ inline int meas_bins_launch(const MeasBinsTwArgs &T, const MeasPiArgs &B, hipStr
     }
     return meas_pi_run(B, st);
 }
+// series: the chunk's table (any form), then the one series kernel
+inline int meas_series_launch(const MeasSeriesTwArgs &T, const MeasSeriesArgs &G, bool pi, hipStream_t st) {
+    const MeasArgs &A = G.B.A;
+    if (A.H > 0) {
+        const long long total = (long long)T.F * A.H * A.len;
+        hipLaunchKernelGGL(acme_meas_series_tw_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, T);
+        const int e = (int)hipGetLastError();
+        if (e) return e;
+    }
+    int waves = 1, groups = 1;
+    meas_shape(A.H, &waves, &groups);
+    const long long P = A.n * A.nrows;
+    const dim3 grid((unsigned)((P + 63) / 64), (unsigned)groups), block(64 * waves);
+    if (pi) hipLaunchKernelGGL(acme_meas_series_kernel<true>, grid, block, 0, st, G);
+    else hipLaunchKernelGGL(acme_meas_series_kernel<false>, grid, block, 0, st, G);
+    return (int)hipGetLastError();
+}
 }  // namespace acme
 #else
 namespace acme {
@@ -469,6 +703,15 @@ inline int meas_pi_launch(const MeasPiTwArgs &T, const MeasPiArgs &B, void *) {
 inline int meas_bins_launch(const MeasBinsTwArgs &T, const MeasPiArgs &B, void *) {
     for (long long idx = 0; idx < (long long)T.F * B.A.H * B.A.len; ++idx) meas_bins_tw(T, idx);
     return meas_pi_run(B);
+}
+inline int meas_series_launch(const MeasSeriesTwArgs &T, const MeasSeriesArgs &G, bool pi, void *) {
+    const MeasArgs &A = G.B.A;
+    for (long long idx = 0; idx < (long long)T.F * A.H * A.len; ++idx) meas_series_tw(T, idx);
+    for (long long q = 0; q < A.n * A.nrows; ++q) {
+        const double *twg = A.tw + (pi ? 2 * (long long)G.B.sgrp[q] * A.H * A.len : 0);
+        for (int u = 0; u <= A.H; ++u) meas_series_chain(A, G.S, twg, pi ? G.B.perm[q] : q, u);
+    }
+    return 0;
 }
 }  // namespace acme
 #endif

@@ -65,6 +65,7 @@ ABI_SYMBOLS = [
     "acme_batch_set_source_clock", "acme_batch_get_source_clock", "acme_batch_run_sources", "acme_batch_run_sources_async",
     "acme_batch_render_sources",
     "acme_batch_set_source_multisine", "acme_batch_set_measurement_bins",
+    "acme_batch_set_measurement_series", "acme_batch_get_measurement_series",
 ]
 
 SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE = 1, 2, 3, 4
@@ -170,6 +171,8 @@ class Library:
         L.acme_batch_set_source_multisine.argtypes = [vp, C.c_int, C.c_longlong, C.c_int, lp, lp, dp, dp]
         L.acme_batch_set_measurement_bins.argtypes = [vp, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, lp, C.c_int, ip,
                                                       C.c_ulonglong]
+        L.acme_batch_set_measurement_series.argtypes = [vp, C.c_longlong, C.c_longlong, C.c_longlong]
+        L.acme_batch_get_measurement_series.argtypes = [vp, C.c_longlong, C.c_longlong, dp, lp]
 
     def check(self, rc):
         if rc < 0:
@@ -248,6 +251,68 @@ class Measurement:
         m.count, m.rows = parts[0].count, parts[0].rows
         for k in ("mean", "rms", "min", "max", "harmonics"):
             setattr(m, k, np.concatenate([getattr(p, k) for p in parts]))
+        return m
+
+
+class MeasurementSeries:
+    """What ``ModelRunner.measurement_series()`` returns: the windows ``first ... first + len() - 1`` of a series.  Indexing
+    yields a window's ``Measurement``; ``counts`` (W,) the samples measured so far per window, ``complete`` the number of
+    windows with ``count == win``, ``starts`` (W,) each window's first sample counted from arming; ``mean``, ``rms``, ``min``,
+    ``max``, ``peak`` stacked (W, N, nrows), ``harmonics`` / ``bins`` (W, N, nrows, H); ``thd()`` / ``imd()`` (W, N, nrows)."""
+
+    def __init__(self, out, counts, rows, start, win, hop, first=0):
+        self.counts = np.asarray(counts, dtype=np.int64)
+        self.rows = tuple(rows)
+        self.win, self.hop, self.first = int(win), int(hop), int(first)
+        self.starts = int(start) + (self.first + np.arange(len(self.counts), dtype=np.int64)) * self.hop
+        self.mean, self.rms, self.min, self.max = (out[..., k].copy() for k in range(4))
+        self.harmonics = out[..., 4::2] + 1j * out[..., 5::2]
+
+    def __len__(self):
+        return len(self.counts)
+
+    def __getitem__(self, w):
+        w = range(len(self))[w]         # (negative indices, IndexError beyond the series)
+        m = Measurement.__new__(Measurement)
+        m.count, m.rows = int(self.counts[w]), self.rows
+        for k in ("mean", "rms", "min", "max", "harmonics"):
+            setattr(m, k, getattr(self, k)[w])
+        return m
+
+    @property
+    def complete(self):
+        return int((self.counts == self.win).sum())
+
+    @property
+    def bins(self):
+        return self.harmonics
+
+    @property
+    def peak(self):
+        return np.maximum(np.abs(self.min), np.abs(self.max))
+
+    def thd(self):
+        """total harmonic distortion per window (W, N, nrows); needs H >= 2"""
+        a = np.abs(self.harmonics)
+        if a.shape[-1] < 2:
+            raise ValueError("THD needs a measurement of at least 2 harmonics")
+        return np.sqrt((a[..., 1:] ** 2).sum(axis=-1)) / a[..., 0]
+
+    def imd(self, fundamental_bins, product_bins):
+        """intermodulation distortion per window (W, N, nrows), as ``Measurement.imd``"""
+        a = np.abs(self.harmonics)
+        fb, pb = list(fundamental_bins), list(product_bins)
+        if not fb or not pb:
+            raise ValueError("IMD needs at least one fundamental bin and one product bin")
+        return np.sqrt((a[..., pb] ** 2).sum(axis=-1)) / np.sqrt((a[..., fb] ** 2).sum(axis=-1))
+
+    @classmethod
+    def concatenate(cls, parts):
+        m = cls.__new__(cls)
+        for k in ("counts", "rows", "win", "hop", "first", "starts"):
+            setattr(m, k, getattr(parts[0], k))
+        for k in ("mean", "rms", "min", "max", "harmonics"):
+            setattr(m, k, np.concatenate([getattr(p, k) for p in parts], axis=1))
         return m
 
 
@@ -367,6 +432,7 @@ class ModelRunner:
         self._warned = 0
         self._os = (1, 1, 1)            # oversampling: factor, interpolation taps, decimation taps
         self._meas = None               # measurement: (harmonics, measured rows) while armed
+        self._series = (0, None)        # (the armed start, (win, hop, windows) of a series or None)
         self._sources = {}              # input row -> kind, while the row has a source
         self._sine = {}                 # input row -> (f_den, f_num as armed) of its sine source
         self._progress_cb = None
@@ -456,6 +522,7 @@ class ModelRunner:
             self.lib.check(self.lib.L.acme_batch_set_measurement_per_instance(self.h, spec[0], spec[1], int(f_den), fp,
                                                                               spec[4], spec[5]))
         self._meas = (int(harmonics), rows)
+        self._series = (int(start), None)
         return self
 
     def set_measurement_bins(self, coef, start=0, length=0, rows=None, f_den=None, f_num=None, tones_from_source=None):
@@ -489,6 +556,7 @@ class ModelRunner:
         self.lib.check(self.lib.L.acme_batch_set_measurement_bins(self.h, spec[0], spec[1], int(f_den), tones, fp, ca.shape[0],
                                                                   _ip(ca), spec[5]))
         self._meas = (ca.shape[0], rows)
+        self._series = (int(start), None)
         return self
 
     def measurement_plan(self):
@@ -508,7 +576,33 @@ class ModelRunner:
         """switch the measurement off (``acme_batch_clear_measurement``)"""
         self.lib.check(self.lib.L.acme_batch_clear_measurement(self.h))
         self._meas = None
+        self._series = (0, None)
         return self
+
+    def set_measurement_series(self, win, hop=None, windows=1):
+        """Turn the armed measurement's one window into a series (``acme_batch_set_measurement_series``): ``windows`` windows
+        of ``win`` samples, one every ``hop`` samples (None: ``win``, back to back), window w over
+        ``start + w hop <= n < start + w hop + win`` -- all accumulated in the same pass, each bit for bit the single window
+        armed there.  Needs a measurement armed with ``length=0`` that has not been fed yet; ``measurement_series`` reads it."""
+        if self._meas is None:
+            raise AcmeError("no measurement is armed")
+        hop = win if hop is None else hop
+        self.lib.check(self.lib.L.acme_batch_set_measurement_series(self.h, int(win), int(hop), int(windows)))
+        self._series = (self._series[0], (int(win), int(hop), int(windows)))
+        return self
+
+    def measurement_series(self, first=0, n=None):
+        """the windows ``first ... first + n - 1`` (None: to the last) of the series so far
+        (``acme_batch_get_measurement_series``): a ``MeasurementSeries``"""
+        if self._meas is None or self._series[1] is None:
+            raise AcmeError("no measurement series is set")
+        (H, rows), (start, (win, hop, W)) = self._meas, self._series
+        n = W - int(first) if n is None else int(n)
+        out = np.empty((max(n, 0), self.n, len(rows), 4 + 2 * H))
+        counts = np.zeros(max(n, 0), dtype=np.int64)
+        self.lib.check(self.lib.L.acme_batch_get_measurement_series(self.h, int(first), n, _dp(out),
+                                                                    counts.ctypes.data_as(C.POINTER(C.c_longlong))))
+        return MeasurementSeries(out, counts, rows, start, win, hop, first)
 
     def reset_measurement(self):
         """zero the accumulators and restart the window's clock (``acme_batch_reset_measurement``)"""
@@ -519,6 +613,8 @@ class ModelRunner:
         """the armed measurement's results so far (``acme_batch_get_measurement``): a ``Measurement``"""
         if self._meas is None:
             raise AcmeError("no measurement is armed")
+        if self._series[1] is not None:
+            raise AcmeError("the measurement has a series of windows: use measurement_series()")
         H, rows = self._meas
         out = np.empty((self.n, len(rows), 4 + 2 * H))
         count = C.c_longlong(0)
@@ -1115,6 +1211,17 @@ class MultiDeviceRunner:
     def measurement(self):
         """the shards' ``Measurement`` results, concatenated along the instances"""
         return Measurement.concatenate([r.measurement() for r in self.runners if r is not None])
+
+    def set_measurement_series(self, win, hop=None, windows=1):
+        """``ModelRunner.set_measurement_series`` on every device's batch"""
+        for r in self.runners:
+            if r is not None:
+                r.set_measurement_series(win, hop, windows)
+        return self
+
+    def measurement_series(self, first=0, n=None):
+        """the shards' ``MeasurementSeries`` results, concatenated along the instances"""
+        return MeasurementSeries.concatenate([r.measurement_series(first, n) for r in self.runners if r is not None])
 
     def measure(self, u=None, check=True, T=None):
         """``run`` with y = NULL on every device (``u``: (N, T, nu), the ABI's layout); only the measurements are fed.

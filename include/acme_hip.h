@@ -312,6 +312,30 @@ int acme_batch_get_measurement_plan(acme_batch *b, long long *n_groups, long lon
 int acme_batch_set_measurement_bins(acme_batch *b, long long start, long long length, long long f_den, int tones,
                                     long long *f_num /* host, [tones][N], only read */, int bins,
                                     const int *coef /* host, [bins][tones] */, unsigned long long rows);
+/* A SERIES of windows: the armed measurement (any of the three forms, armed with length = 0, no sample fed since arming or
+ * the last reset) measures `windows` windows of `win` samples, one every `hop` samples, all in the same pass over y -- a level
+ * or a harmonic as a function of time: has the THD settled, a tone burst, the recovery after overload, a parameter stepped in
+ * time with a settle gap (hop > win) between the readings.
+ *   window w (0 <= w < windows) covers the samples start + w hop <= n < start + w hop + win, 1 <= win <= hop; the samples of a
+ *   gap and those behind the last window belong to no window.
+ * Window w holds, BIT FOR BIT, what the same form armed with start' = start + w hop, length' = win accumulates on an identical
+ * run: the twiddle's phase is window-relative (m' = n - start - w hop), every accumulator one chain in sample order from its
+ * start value.  Nothing depends on where chunks, slices or calls end, on the memory kind, the entry point, the oversampling
+ * factor or on whether y is stored; a window the end of a run cuts is partial (its count the samples seen so far) and goes
+ * on in the next call.  The accumulators take windows x (4 + 2H) x N nrows doubles of device memory.
+ * ACME_ERR_INVALID (the message names the argument): no measurement armed, length != 0, samples already fed, win < 1,
+ * hop < win, windows outside 1 ... ACME_MAX_SERIES_WINDOWS, start + (windows - 1) hop + win beyond 64 bits.  With a series
+ * acme_batch_get_measurement is refused (ACME_ERR_INVALID, naming the getter below), _reset_measurement restarts every window
+ * and the clock, arming any form or _clear_measurement removes the series, acme_batch_get_measurement_plan is unchanged and
+ * acme_batch_set_matrices carries the series with the accumulators.  A batch without a series launches and allocates what
+ * it always did. */
+#define ACME_MAX_SERIES_WINDOWS 1048576
+int acme_batch_set_measurement_series(acme_batch *b, long long win, long long hop, long long windows);
+/* windows first ... first + n - 1 of the series: out[n][N][nrows][4 + 2H], each window in the format and scaling of
+ * acme_batch_get_measurement (may be NULL); counts[n]: the samples measured so far per window (may be NULL).  A window never
+ * reached has count 0 and reads NaN / +-inf as a fresh single window does.  ACME_ERR_INVALID without a series, or when
+ * first + n exceeds the series' windows.  Joins a pending acme_batch_run_async and synchronises the device. */
+int acme_batch_get_measurement_series(acme_batch *b, long long first, long long n, double *out, long long *counts);
 /* switch the measurement off (y = NULL is refused again) */
 int acme_batch_clear_measurement(acme_batch *b);
 /* zero the accumulators and restart the window's clock (the armed parameters stay) */

@@ -37,7 +37,7 @@ import ACME: run!, solve, hasconverged, needediterations, set_resabstol!,
 export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host_buffers!, release_host_buffers!, set_isolation!, set_balance!,
        MeasureSpec, Measurement, set_measurement!, clear_measurement!, reset_measurement!, measurement, measurement_plan, measure!,
        set_source!, clear_source!, source_clock, source_clock!, run_sources!, render_sources,
-       set_source_multisine!, set_measurement_bins!
+       set_source_multisine!, set_measurement_bins!, set_measurement_series!, measurement_series
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
 
@@ -49,6 +49,7 @@ const ACME_SOLVER_SIMPLE, ACME_SOLVER_HOMOTOPY, ACME_SOLVER_CACHING_HOMOTOPY = C
 const ACME_MEM_HOST, ACME_MEM_DEVICE = Cint(0), Cint(1)
 const ACME_MAX_OVERSAMPLING = 16
 const ACME_MAX_HARMONICS = 32
+const ACME_MAX_SERIES_WINDOWS = 1048576
 const ACME_SOURCE_CONST, ACME_SOURCE_SINE, ACME_SOURCE_TABLE, ACME_SOURCE_MULTISINE = Cint(1), Cint(2), Cint(3), Cint(4)
 const ACME_MAX_SOURCE_TABLE = 16777216
 const ACME_MAX_SOURCE_TONES = 4
@@ -562,6 +563,41 @@ function measurement(r::BatchRunner)
     check(ccall((:acme_batch_get_measurement, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ref{Clonglong}), r.h, out, count))
     return Measurement(count[], rows, out[1, :, :], out[2, :, :], out[3, :, :], out[4, :, :],
                        complex.(out[5:2:end, :, :], out[6:2:end, :, :]))
+end
+
+"""
+    set_measurement_series!(runner, win; hop=win, windows=1)
+
+Turn the armed measurement's one window into a series (`acme_batch_set_measurement_series`): `windows` windows of `win`
+samples, one every `hop` samples, window `w` (0-based) over `start + w hop <= n < start + w hop + win` -- all accumulated in
+the same pass, each bit for bit the single window armed there.  Needs a measurement armed with `length = 0` that has not
+been fed yet.
+"""
+function set_measurement_series!(r::BatchRunner, win::Integer; hop::Integer=win, windows::Integer=1)
+    r.meas === nothing && error("no measurement is armed")
+    check(ccall((:acme_batch_set_measurement_series, lib), Cint, (Ptr{Cvoid}, Clonglong, Clonglong, Clonglong),
+                r.h, win, hop, windows))
+    return r
+end
+
+"""
+    measurement_series(runner, first, n) -> Vector{Measurement}
+
+The windows `first ... first + n - 1` (0-based) of the series so far (`acme_batch_get_measurement_series`), each a
+`Measurement` with its own `count`; a window never reached has count 0.
+"""
+function measurement_series(r::BatchRunner, first::Integer, n::Integer)
+    spec = r.meas
+    spec === nothing && error("no measurement is armed")
+    ny = ACME.ny(r.model)
+    rows = spec.rows == 0 ? collect(1:min(ny, 64)) : [k for k in 1:64 if (spec.rows >> (k - 1)) & 1 == 1]
+    H = Int(spec.harmonics)
+    out = Array{Float64,4}(undef, 4 + 2H, length(rows), r.n, n)     # the ABI's [n][N][nrows][4 + 2H]
+    counts = Vector{Clonglong}(undef, n)
+    check(ccall((:acme_batch_get_measurement_series, lib), Cint,
+                (Ptr{Cvoid}, Clonglong, Clonglong, Ptr{Cdouble}, Ptr{Clonglong}), r.h, first, n, out, counts))
+    return [Measurement(counts[w], rows, out[1, :, :, w], out[2, :, :, w], out[3, :, :, w], out[4, :, :, w],
+                        complex.(out[5:2:end, :, :, w], out[6:2:end, :, :, w])) for w in 1:n]
 end
 
 """
