@@ -161,6 +161,12 @@ struct acme_batch {
         long long *d_kbin_g = nullptr;           // [F][H]: the groups' reduced bin frequencies
         // series (acme_batch_set_measurement_series): W windows of win samples, one every hop; d_acc is [W][4 + 2H][N nrows]
         long long win = 0, hop = 0, W = 0;       // W = 0: one window, [start, start + length)
+        // fold (acme_batch_set_measurement_fold): the window folded onto a period per instance, slot m mod period
+        bool fold = false;
+        long long fold_pmax = 0;                 // the longest period: the accumulators' pitch
+        std::vector<long long> fold_per;         // [N]: the instances' periods
+        long long *d_fold_per = nullptr;         // [N]
+        double *d_fold = nullptr;                // [N nrows][fold_pmax] sums, from 0.0
     } meas;
     // Input rows generated on the device (acme_batch_set_source_*, acme_source.h): the rows' descriptions and per-instance
     // parameters in device memory, the source clock
@@ -742,6 +748,7 @@ static void meas_release(acme_batch::Measurement &M) {
     (void)be::dfree(M.d_acc); (void)be::dfree(M.d_tw); (void)be::dfree(M.d_ys);
     (void)be::dfree(M.d_fnum_g); (void)be::dfree(M.d_perm); (void)be::dfree(M.d_sgrp); (void)be::dfree(M.d_wgrp);
     (void)be::dfree(M.d_kbin_g);
+    (void)be::dfree(M.d_fold_per); (void)be::dfree(M.d_fold);
     M = acme_batch::Measurement{};
 }
 
@@ -1309,15 +1316,18 @@ static int meas_step(acme_batch *b, const double *y, long long n, long long pitc
         if (M.bins) {
             const MeasBinsTwArgs W{M.d_tw, M.d_kbin_g, s - M.start, len, M.f_den, M.H, M.F};
             HIPCHK(meas_bins_launch(W, MeasPiArgs{A, M.d_perm, M.d_sgrp, M.d_wgrp}, st));
-            continue;
-        }
-        if (M.pi) {
+        } else if (M.pi) {
             const MeasPiTwArgs W{M.d_tw, M.d_fnum_g, s - M.start, len, M.f_den, M.H, M.F};
             HIPCHK(meas_pi_launch(W, MeasPiArgs{A, M.d_perm, M.d_sgrp, M.d_wgrp}, st));
-            continue;
+        } else {
+            const MeasTwArgs W{M.d_tw, s - M.start, len, M.f_num, M.f_den, M.H};
+            HIPCHK(meas_launch(W, A, st));
         }
-        const MeasTwArgs W{M.d_tw, s - M.start, len, M.f_num, M.f_den, M.H};
-        HIPCHK(meas_launch(W, A, st));
+        if (M.fold) {   // one more kernel on the same chunk of y
+            MeasFoldArgs G{y, M.d_fold, M.d_fold_per, b->N, len, pitch, s - M.pos, s - M.start, M.fold_pmax, A.ny, M.nrows, {}};
+            memcpy(G.row, M.row, sizeof(G.row));
+            HIPCHK(meas_fold_launch(G, st));
+        }
     }
     M.pos += n;
     return ACME_OK;
@@ -2135,6 +2145,10 @@ static int meas_zero(acme_batch *b) {
             for (size_t p = 0; p < P; ++p) a[w * slot + k * P + p] = meas_init(k);
     for (size_t w = 0; slot && w < W; w += per)
         HIPCHK(be::copy_h2d(M.d_acc + w * slot, a.data(), sizeof(double) * slot * std::min(per, W - w)));
+    if (M.fold) {       // (the periods stay)
+        HIPCHK(meas_fold_zero(M.d_fold, P * (size_t)M.fold_pmax));
+        HIPCHK(be::device_sync());
+    }
     M.pos = 0;
     return ACME_OK;
 }
@@ -2304,6 +2318,7 @@ int acme_batch_set_measurement_series(acme_batch *b, long long win, long long ho
     if (!b) return fail(ACME_ERR_INVALID, "null batch");
     acme_batch::Measurement &M = b->meas;
     if (!M.on) return fail(ACME_ERR_INVALID, "measurement series: no measurement is armed");
+    if (M.fold) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a fold (a fold per window is not supported)");
     if (M.length != 0) return fail(ACME_ERR_INVALID, "measurement series: the armed measurement's length must be 0 (the series sets the windows)");
     if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement series: samples have been fed since arming (arm or reset the measurement first)");
     if (win < 1) return fail(ACME_ERR_INVALID, "measurement series: win must be >= 1");
@@ -2360,6 +2375,75 @@ int acme_batch_get_measurement_series(acme_batch *b, long long first, long long 
         }
     }
     return ACME_OK;
+}
+
+int acme_batch_set_measurement_fold(acme_batch *b, long long period, long long *period_i) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    acme_batch::Measurement &M = b->meas;
+    if (!M.on) return fail(ACME_ERR_INVALID, "measurement fold: no measurement is armed");
+    if (M.W) return fail(ACME_ERR_UNSUPPORTED, "measurement fold: the measurement has a series of windows (a fold per window is not supported)");
+    if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement fold: samples have been fed since arming (arm or reset the measurement first)");
+    const std::string range = " outside 1 ... " + std::to_string(MEAS_MAX_FOLD_PERIOD);
+    if (!period_i && (period < 1 || period > MEAS_MAX_FOLD_PERIOD)) return fail(ACME_ERR_INVALID, "measurement fold: period is" + range);
+    std::vector<long long> per((size_t)b->N, period);
+    long long pmax = 0;
+    for (long long i = 0; i < b->N; ++i) {
+        if (period_i) per[(size_t)i] = period_i[i];
+        if (per[(size_t)i] < 1 || per[(size_t)i] > MEAS_MAX_FOLD_PERIOD)
+            return fail(ACME_ERR_INVALID, "measurement fold: period_i of instance " + std::to_string(i) + " is" + range);
+        pmax = std::max(pmax, per[(size_t)i]);
+    }
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    (void)be::dfree(M.d_fold_per); (void)be::dfree(M.d_fold);       // (a fold set again replaces the earlier one)
+    M.d_fold_per = nullptr;
+    M.d_fold = nullptr;
+    M.fold = false;
+    const size_t count = (size_t)b->N * (size_t)M.nrows * (size_t)pmax;
+    HIPCHK(be::dmalloc((void **)&M.d_fold_per, sizeof(long long) * per.size()));
+    HIPCHK(be::dmalloc((void **)&M.d_fold, sizeof(double) * count));
+    HIPCHK(be::copy_h2d(M.d_fold_per, per.data(), sizeof(long long) * per.size()));
+    HIPCHK(meas_fold_zero(M.d_fold, count));
+    HIPCHK(be::device_sync());
+    M.fold_per = std::move(per);
+    M.fold_pmax = pmax;
+    M.fold = true;
+    return ACME_OK;
+}
+
+static int get_measurement_fold(acme_batch *b, double *out, long long *period, long long *count, bool sums) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const acme_batch::Measurement &M = b->meas;
+    if (!M.on || !M.fold) return fail(ACME_ERR_INVALID, "no measurement fold is set");
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    const long long end = M.length ? M.start + M.length : LLONG_MAX;
+    const long long cnt = (M.pos < end ? M.pos : end) - M.start, c = cnt > 0 ? cnt : 0;
+    if (count) *count = c;
+    if (period) memcpy(period, M.fold_per.data(), sizeof(long long) * M.fold_per.size());
+    if (!out) return ACME_OK;
+    const size_t pm = (size_t)M.fold_pmax, pairs = (size_t)b->N * M.nrows;
+    if (pairs) HIPCHK(be::copy_d2h(out, M.d_fold, sizeof(double) * pairs * pm));     // (the accumulators' layout is the result's)
+    for (size_t p = 0; p < pairs; ++p) {
+        const long long P = M.fold_per[p / (size_t)M.nrows];
+        double *o = out + p * pm;
+        for (long long s = 0; s < M.fold_pmax; ++s) {
+            const long long cs = s < P && c > s ? (c - s - 1) / P + 1 : 0;      // the samples slot s has received
+            o[s] = cs == 0 ? NAN : sums ? o[s] : o[s] / (double)cs;
+        }
+    }
+    return ACME_OK;
+}
+
+int acme_batch_get_measurement_fold(acme_batch *b, double *out, long long *period, long long *count) {
+    return get_measurement_fold(b, out, period, count, false);
+}
+
+int acme_batch_get_measurement_fold_sums(acme_batch *b, double *out) {
+    if (b && !out) return fail(ACME_ERR_INVALID, "measurement fold sums: out is null");
+    return get_measurement_fold(b, out, nullptr, nullptr, true);
 }
 
 int acme_batch_clear_measurement(acme_batch *b) { return set_measurement(b, nullptr); }

@@ -51,6 +51,18 @@
 // window's first sample starts from meas_init in registers, a window that continues from an earlier chunk loads its slot,
 // and the window's last sample -- or the chunk's -- stores the slot.  A tile that lies wholly in a gap is not staged.
 //
+// FOLD (acme_batch_set_measurement_fold): the window folded onto a period of P_i samples per instance, 1 <= P_i <=
+// MEAS_MAX_FOLD_PERIOD -- slot s = m mod P_i of pair p accumulates fold[p][s] += y, ONE chain per slot, plain additions in
+// sample order from 0.0.  The accumulators are [N nrows][Pmax], Pmax = max P_i.  One more kernel per chunk behind the
+// measurement's own (acme_meas_fold_kernel), on the same chunk of y: ONE WAVE PER PAIR, so the period is wave-uniform and
+// per-instance periods need no plan.  The phase ph = m0 mod P of the chunk's first sample is formed once per wave in 64-bit
+// integers; lane l of block jb then owns the chunk's sample c = 64 jb + l < min(len, P) and with it the slot (ph + c) mod P,
+// whose later samples follow at c + P, c + 2 P, ...: consecutive lanes read consecutive samples at every step (512
+// contiguous bytes per wave instruction at ny = 1), every sample of the chunk is read once, a slot is loaded once and stored
+// once, and a chunk shorter than the period touches the len slots it covers and no other.  Several blocks run side by side
+// (independent chains: their loads are in flight together); a period below 64 leaves the lanes at and beyond P idle and
+// takes several of a slot's samples ahead of its chain instead.
+//
 // The per-element functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with g++).
 #pragma once
@@ -177,6 +189,31 @@ ACME_HD inline void meas_series_tw(const MeasSeriesTwArgs &A, long long idx) {
     if (!meas_series_at(A.S, A.S.s0 + t, &w, &m)) return;
     if (A.bins) meas_twiddle(1, m, A.fg[g * A.H + h], A.f_den, &A.tw[2 * idx], &A.tw[2 * idx + 1]);
     else meas_twiddle(h + 1, m, A.fg ? A.fg[g] : A.f_num, A.f_den, &A.tw[2 * idx], &A.tw[2 * idx + 1]);
+}
+
+// fold: the chunk's first sample is number m0 >= 0 of the window (n - start)
+constexpr long long MEAS_MAX_FOLD_PERIOD = 65536;
+constexpr int MEAS_FOLD_WAVES = 4;          // pairs (one wave each) per block
+
+struct MeasFoldArgs {
+    const double *y;            // instance i, sample t, row r at y[(i * pitch + t0 + t) * ny + r]
+    double *fold;               // [n * nrows][pmax]
+    const long long *per;       // [n]: the instances' periods, 1 <= per[i] <= pmax
+    long long n, len, pitch, t0, m0, pmax;
+    int ny, nrows;
+    unsigned char row[64];      // the measured rows, ascending
+};
+
+// one pair over the chunk, sample after sample into the sample's slot (the reference order every backend keeps)
+ACME_HD inline void meas_fold_chain(const MeasFoldArgs &A, long long p) {
+    const long long i = p / A.nrows, P = A.per[i];
+    const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    double *f = A.fold + p * A.pmax;
+    long long s = A.m0 % P;
+    for (long long t = 0; t < A.len; ++t) {
+        f[s] += yp[t * A.ny];
+        if (++s == P) s = 0;
+    }
 }
 
 // NaN sticks: once an accumulator is NaN it stays so
@@ -618,7 +655,67 @@ __global__ __launch_bounds__(1024) void acme_meas_series_kernel(acme::MeasSeries
         if (u == 0) { acc[2 * P] = a2; acc[3 * P] = a3; }
     }
 }
+
+// fold: U blocks of 64 of the chunk's first `cover` samples from cb on, K periods a step.  Lane l of block u owns sample
+// c = cb + 64 u + l and its slot; the loads of a step are issued together, the additions follow per slot in sample order.
+template <int U, int K>
+__device__ inline void acme_meas_fold_span(const double *yp, double *f, long long cb, long long cover, long long len,
+                                           long long ph, long long P, int ny, int lane) {
+    double a[U];
+    long long s[U];
+    bool on[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const long long c = cb + 64 * u + lane;
+        on[u] = c < cover;
+        s[u] = ph + c < P ? ph + c : ph + c - P;        // (ph < P and c < P: one wrap at most)
+        a[u] = on[u] ? f[s[u]] : 0.0;
+    }
+    for (long long tb = cb; tb < len; tb += K * P) {
+        double v[K][U];
+        bool h[K][U];
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const long long t = tb + k * P + 64 * u + lane;
+                h[k][u] = on[u] && t < len;
+                v[k][u] = h[k][u] ? yp[t * ny] : 0.0;
+            }
+#pragma unroll
+        for (int k = 0; k < K; ++k)
+#pragma unroll
+            for (int u = 0; u < U; ++u)
+                if (h[k][u]) a[u] += v[k][u];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+        if (on[u]) f[s[u]] = a[u];
+}
+
+// block: MEAS_FOLD_WAVES pairs, a wave each (the period, the phase and the pair's addresses are wave-uniform)
+__global__ __launch_bounds__(64 * acme::MEAS_FOLD_WAVES) void acme_meas_fold_kernel(acme::MeasFoldArgs A) {
+    using namespace acme;
+    const int lane = threadIdx.x & 63;
+    const long long p = (long long)blockIdx.x * MEAS_FOLD_WAVES + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (p >= A.n * A.nrows) return;
+    const long long i = p / A.nrows, P = A.per[i];
+    const long long ph = A.m0 % P;                      // once per wave, in 64-bit integers
+    const long long cover = A.len < P ? A.len : P;      // the slots the chunk reaches: its first min(len, P) samples'
+    const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    double *f = A.fold + p * A.pmax;
+    long long cb = 0;
+    for (; cover - cb > 64; cb += 256) acme_meas_fold_span<4, 2>(yp, f, cb, cover, A.len, ph, P, A.ny, lane);
+    if (cb < cover) acme_meas_fold_span<1, 8>(yp, f, cb, cover, A.len, ph, P, A.ny, lane);
+}
 namespace acme {
+inline int meas_fold_launch(const MeasFoldArgs &A, hipStream_t st) {
+    const long long pairs = A.n * A.nrows;
+    hipLaunchKernelGGL(acme_meas_fold_kernel, dim3((unsigned)((pairs + MEAS_FOLD_WAVES - 1) / MEAS_FOLD_WAVES)),
+                       dim3(64 * MEAS_FOLD_WAVES), 0, st, A);
+    return (int)hipGetLastError();
+}
+inline int meas_fold_zero(double *fold, size_t count) { return (int)hipMemset(fold, 0, sizeof(double) * count); }
 inline int meas_launch(const MeasTwArgs &T, const MeasArgs &A, hipStream_t st) {
     if (A.H > 0) {
         hipLaunchKernelGGL(acme_meas_tw_kernel, dim3((unsigned)((A.H * A.len + 255) / 256)), dim3(256), 0, st, T);
@@ -681,6 +778,14 @@ inline int meas_series_launch(const MeasSeriesTwArgs &T, const MeasSeriesArgs &G
 }  // namespace acme
 #else
 namespace acme {
+inline int meas_fold_launch(const MeasFoldArgs &A, void *) {
+    for (long long p = 0; p < A.n * A.nrows; ++p) meas_fold_chain(A, p);
+    return 0;
+}
+inline int meas_fold_zero(double *fold, size_t count) {
+    std::fill(fold, fold + count, 0.0);
+    return 0;
+}
 inline int meas_launch(const MeasTwArgs &T, const MeasArgs &A, void *) {
     for (long long idx = 0; idx < A.H * A.len; ++idx) meas_tw(T, idx);
     for (long long p = 0; p < A.n * A.nrows; ++p)

@@ -66,10 +66,12 @@ ABI_SYMBOLS = [
     "acme_batch_render_sources",
     "acme_batch_set_source_multisine", "acme_batch_set_measurement_bins",
     "acme_batch_set_measurement_series", "acme_batch_get_measurement_series",
+    "acme_batch_set_measurement_fold", "acme_batch_get_measurement_fold", "acme_batch_get_measurement_fold_sums",
 ]
 
 SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE = 1, 2, 3, 4
 MAX_SOURCE_TONES = 4
+MAX_FOLD_PERIOD = 65536
 _SOURCE_KINDS = {"const": SOURCE_CONST, "sine": SOURCE_SINE, "table": SOURCE_TABLE, "multisine": SOURCE_MULTISINE,
                  SOURCE_CONST: SOURCE_CONST, SOURCE_SINE: SOURCE_SINE, SOURCE_TABLE: SOURCE_TABLE, SOURCE_MULTISINE: SOURCE_MULTISINE}
 
@@ -173,6 +175,9 @@ class Library:
                                                       C.c_ulonglong]
         L.acme_batch_set_measurement_series.argtypes = [vp, C.c_longlong, C.c_longlong, C.c_longlong]
         L.acme_batch_get_measurement_series.argtypes = [vp, C.c_longlong, C.c_longlong, dp, lp]
+        L.acme_batch_set_measurement_fold.argtypes = [vp, C.c_longlong, lp]
+        L.acme_batch_get_measurement_fold.argtypes = [vp, dp, lp, lp]
+        L.acme_batch_get_measurement_fold_sums.argtypes = [vp, dp]
 
     def check(self, rc):
         if rc < 0:
@@ -316,6 +321,39 @@ class MeasurementSeries:
         return m
 
 
+class MeasurementFold:
+    """What ``ModelRunner.measurement_fold()`` returns: the measured window folded onto one period per instance
+    (synchronous averaging).  ``mean`` (N, nrows, Pmax): slot s of instance i, s < ``period[i]``, holds the mean of the
+    window's samples m with m mod period[i] == s; slots no sample has reached, and the slots at and beyond an instance's
+    period, are NaN.  ``period`` (N,), ``count`` the samples measured, ``rows`` the measured output rows."""
+
+    def __init__(self, mean, period, count, rows):
+        self.mean, self.period, self.count, self.rows = mean, np.asarray(period, dtype=np.int64), int(count), tuple(rows)
+
+    def slot_counts(self, i):
+        """the samples each slot of instance ``i`` has received (period[i],)"""
+        P = int(self.period[i])
+        s = np.arange(P)
+        return np.where(self.count > s, (self.count - s - 1) // P + 1, 0)
+
+    def spectrum(self, i, row=0):
+        """the complex amplitudes of the lines k / period[i] of the sample rate, k = 0 ... period[i] // 2, of instance
+        ``i``'s folded period (``row``: index into ``rows``): ``2 / P rfft(mean[i, row, :P])`` -- the scaling of a
+        measurement's A_h, line k the harmonic A_k of the fundamental 1 / P --, the DC line (the mean) unscaled"""
+        P = int(self.period[i])
+        a = np.fft.rfft(self.mean[i, row, :P]) * (2.0 / P)
+        a[0] *= 0.5
+        return a
+
+    @classmethod
+    def concatenate(cls, parts):
+        if any((p.count, p.rows) != (parts[0].count, parts[0].rows) for p in parts):
+            raise ValueError("the shards' folds differ in their sample counts or measured rows")
+        pm = max(p.mean.shape[2] for p in parts)
+        mean = np.concatenate([np.pad(p.mean, ((0, 0), (0, 0), (0, pm - p.mean.shape[2])), constant_values=np.nan) for p in parts])
+        return cls(mean, np.concatenate([p.period for p in parts]), parts[0].count, parts[0].rows)
+
+
 def measure_spec(ny, start=0, length=0, f0=None, harmonics=0, rows=None):
     """((start, length, f_num, f_den, harmonics, row mask), measured rows) -- acme_batch_set_measurement's arguments -- from
     ``ModelRunner.set_measurement``'s: ``f0`` a Fraction of fs or
@@ -433,6 +471,7 @@ class ModelRunner:
         self._os = (1, 1, 1)            # oversampling: factor, interpolation taps, decimation taps
         self._meas = None               # measurement: (harmonics, measured rows) while armed
         self._series = (0, None)        # (the armed start, (win, hop, windows) of a series or None)
+        self._fold = False              # a fold is set on the armed measurement
         self._sources = {}              # input row -> kind, while the row has a source
         self._sine = {}                 # input row -> (f_den, f_num as armed) of its sine source
         self._progress_cb = None
@@ -523,6 +562,7 @@ class ModelRunner:
                                                                               spec[4], spec[5]))
         self._meas = (int(harmonics), rows)
         self._series = (int(start), None)
+        self._fold = False
         return self
 
     def set_measurement_bins(self, coef, start=0, length=0, rows=None, f_den=None, f_num=None, tones_from_source=None):
@@ -557,6 +597,7 @@ class ModelRunner:
                                                                   _ip(ca), spec[5]))
         self._meas = (ca.shape[0], rows)
         self._series = (int(start), None)
+        self._fold = False
         return self
 
     def measurement_plan(self):
@@ -577,6 +618,7 @@ class ModelRunner:
         self.lib.check(self.lib.L.acme_batch_clear_measurement(self.h))
         self._meas = None
         self._series = (0, None)
+        self._fold = False
         return self
 
     def set_measurement_series(self, win, hop=None, windows=1):
@@ -603,6 +645,54 @@ class ModelRunner:
         self.lib.check(self.lib.L.acme_batch_get_measurement_series(self.h, int(first), n, _dp(out),
                                                                     counts.ctypes.data_as(C.POINTER(C.c_longlong))))
         return MeasurementSeries(out, counts, rows, start, win, hop, first)
+
+    def set_measurement_fold(self, period=None, period_from_source=None):
+        """Fold the armed measurement's window onto one period (``acme_batch_set_measurement_fold``, synchronous averaging):
+        slot ``m mod period`` of the window-relative sample m accumulates y, per instance and measured row -- the steady
+        state's waveform itself in place of y.  ``period``: samples, an int or N ints (one per instance), 1 ... 65536; or
+        ``period_from_source=row``: the period of the sine or multisine source armed on input row ``row``,
+        ``f_den // gcd(f_den, f_num[i])`` per instance (a multisine: the least common multiple over its tones).  Needs an
+        armed measurement (any form, any window) that has not been fed yet; not together with a series;
+        ``measurement_fold`` reads it."""
+        if self._meas is None:
+            raise AcmeError("no measurement is armed")
+        if (period is None) == (period_from_source is None):
+            raise ValueError("a fold needs period or period_from_source")
+        if period_from_source is not None:
+            row = int(period_from_source)
+            if self._sources.get(row) not in (SOURCE_SINE, SOURCE_MULTISINE):
+                raise ValueError(f"input row {row} has no sine or multisine source to take the period from")
+            f_den, f_num = self._sine[row]
+            tones = np.atleast_2d(np.broadcast_to(f_num, (self.n,)) if np.ndim(f_num) < 2 else f_num).astype(np.int64)
+            period = np.lcm.reduce(f_den // np.gcd(f_den, tones), axis=0)
+            if period.max() > MAX_FOLD_PERIOD:
+                i = int(period.argmax())
+                raise ValueError(f"the source's period of instance {i}, {int(period[i])} samples, exceeds {MAX_FOLD_PERIOD}")
+        if np.ndim(period) == 0:
+            self.lib.check(self.lib.L.acme_batch_set_measurement_fold(self.h, int(period), None))
+        else:
+            pa, pp = self._per_instance(period, np.int64, "period")
+            if np.shape(period) != (self.n,):
+                raise DimensionMismatch(f"per-instance periods need {self.n} values")
+            self.lib.check(self.lib.L.acme_batch_set_measurement_fold(self.h, 0, pp))
+        self._fold = True
+        return self
+
+    def measurement_fold(self, raw=False):
+        """the fold so far (``acme_batch_get_measurement_fold``): a ``MeasurementFold``.  ``raw``: ``mean`` holds the slots'
+        sums, undivided (``acme_batch_get_measurement_fold_sums``; the tests pin the chains on them)."""
+        if self._meas is None or not self._fold:
+            raise AcmeError("no measurement fold is set")
+        lp = C.POINTER(C.c_longlong)
+        period, count = np.zeros(self.n, dtype=np.int64), C.c_longlong(0)
+        self.lib.check(self.lib.L.acme_batch_get_measurement_fold(self.h, None, period.ctypes.data_as(lp), C.byref(count)))
+        rows = self._meas[1]
+        out = np.empty((self.n, len(rows), int(period.max(initial=0))))
+        if raw:
+            self.lib.check(self.lib.L.acme_batch_get_measurement_fold_sums(self.h, _dp(out)))
+        else:
+            self.lib.check(self.lib.L.acme_batch_get_measurement_fold(self.h, _dp(out), None, None))
+        return MeasurementFold(out, period, count.value, rows)
 
     def reset_measurement(self):
         """zero the accumulators and restart the window's clock (``acme_batch_reset_measurement``)"""
@@ -1222,6 +1312,20 @@ class MultiDeviceRunner:
     def measurement_series(self, first=0, n=None):
         """the shards' ``MeasurementSeries`` results, concatenated along the instances"""
         return MeasurementSeries.concatenate([r.measurement_series(first, n) for r in self.runners if r is not None])
+
+    def set_measurement_fold(self, period=None, period_from_source=None):
+        """``ModelRunner.set_measurement_fold`` on every device's batch, per-instance periods sliced over the devices"""
+        if period is not None and np.ndim(period) != 0 and len(period) != self.n:
+            raise DimensionMismatch(f"per-instance periods need {self.n} values")
+        for r, (lo, hi) in zip(self.runners, self.ranges):
+            if r is not None:
+                r.set_measurement_fold(period if period is None or np.ndim(period) == 0 else np.asarray(period)[lo:hi],
+                                       period_from_source)
+        return self
+
+    def measurement_fold(self, raw=False):
+        """the shards' ``MeasurementFold`` results, concatenated along the instances (``raw`` as ``ModelRunner``'s)"""
+        return MeasurementFold.concatenate([r.measurement_fold(raw) for r in self.runners if r is not None])
 
     def measure(self, u=None, check=True, T=None):
         """``run`` with y = NULL on every device (``u``: (N, T, nu), the ABI's layout); only the measurements are fed.

@@ -336,6 +336,37 @@ int acme_batch_set_measurement_series(acme_batch *b, long long win, long long ho
  * reached has count 0 and reads NaN / +-inf as a fresh single window does.  ACME_ERR_INVALID without a series, or when
  * first + n exceeds the series' windows.  Joins a pending acme_batch_run_async and synchronises the device. */
 int acme_batch_get_measurement_series(acme_batch *b, long long first, long long n, double *out, long long *counts);
+/* A FOLD of the window onto one period (synchronous averaging): the armed measurement (any of the three forms, armed with any
+ * start / length, no sample fed since arming or the last reset) also accumulates, per instance i with a period of P_i samples
+ * (1 <= P_i <= ACME_MAX_FOLD_PERIOD), measured row j and slot s = m mod P_i of the window-relative sample number m = n - start,
+ *   fold[i][j][s] += y        ONE chain per slot, plain additions in sample order, from 0.0
+ * -- the periodic steady state's waveform itself, N x nrows x P doubles in place of y [N][T][ny]: the clipped wave across a
+ * level sweep, a transfer curve, every harmonic up to Nyquist and the lines where aliasing lands (a host FFT of one period),
+ * THD+N.  Sources and measurement windows run on exact rational frequencies f_num / f_den: the signal's period is the whole
+ * number f_den / gcd(f_num, f_den) of samples (1 kHz at 44.1 kHz: 441).
+ *   period, period_i   period_i = NULL: every instance folds onto `period`; otherwise a HOST array of N entries, instance i
+ *                      folds onto period_i[i] and `period` is ignored (copied by the call, only read)
+ * The fold depends on nothing but the run's samples: chunk, slice and call boundaries, host or device memory, the entry point
+ * (acme_batch_run, _run_const, _run_async, _run_sources), the oversampling factor and whether y is stored change none of its
+ * bits.  The measurement's own accumulators and launches are what they are without a fold; the fold takes one more kernel per
+ * chunk of the window and N nrows max_i P_i doubles of device memory.
+ * ACME_ERR_INVALID (the message names the argument, and the instance of an entry of period_i): no measurement armed, samples
+ * already fed, a period outside 1 ... ACME_MAX_FOLD_PERIOD.  ACME_ERR_UNSUPPORTED together with a series, whichever is set
+ * first: a fold per window is not available.  Setting a fold again replaces the earlier one.  _reset_measurement zeroes the fold
+ * and keeps the periods, arming any form or _clear_measurement removes it, acme_batch_set_matrices carries it with the
+ * accumulators; acme_batch_get_measurement and _get_measurement_plan are unchanged, and so is the refusal with
+ * acme_batch_set_isolation.  A batch without a fold launches and allocates what it always did. */
+#define ACME_MAX_FOLD_PERIOD 65536
+int acme_batch_set_measurement_fold(acme_batch *b, long long period, long long *period_i /* host, [N] or NULL, only read */);
+/* the fold so far: out[N][nrows][Pmax], Pmax = max_i P_i (may be NULL): out[i][j][s] = fold[i][j][s] / c_s, the mean of the
+ * c_s = (count > s ? (count - s - 1) / P_i + 1 : 0) samples slot s has received; a slot nothing has reached, and every slot
+ * s >= P_i, reads NaN, as the mean of an empty window does.  period[N]: the instances' periods (may be NULL); *count: samples
+ * measured, as acme_batch_get_measurement counts them (may be NULL).  ACME_ERR_INVALID without a fold.  Joins a pending
+ * acme_batch_run_async and synchronises the device. */
+int acme_batch_get_measurement_fold(acme_batch *b, double *out, long long *period, long long *count);
+/* the same slots undivided: out[N][nrows][Pmax] (not NULL), out[i][j][s] = fold[i][j][s], the chain's sum itself (the tests pin
+ * it with ==; sums of separate runs can be added before dividing); the slots that read NaN above read NaN here. */
+int acme_batch_get_measurement_fold_sums(acme_batch *b, double *out);
 /* switch the measurement off (y = NULL is refused again) */
 int acme_batch_clear_measurement(acme_batch *b);
 /* zero the accumulators and restart the window's clock (the armed parameters stay) */

@@ -37,7 +37,8 @@ import ACME: run!, solve, hasconverged, needediterations, set_resabstol!,
 export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host_buffers!, release_host_buffers!, set_isolation!, set_balance!,
        MeasureSpec, Measurement, set_measurement!, clear_measurement!, reset_measurement!, measurement, measurement_plan, measure!,
        set_source!, clear_source!, source_clock, source_clock!, run_sources!, render_sources,
-       set_source_multisine!, set_measurement_bins!, set_measurement_series!, measurement_series
+       set_source_multisine!, set_measurement_bins!, set_measurement_series!, measurement_series,
+       set_measurement_fold!, measurement_fold
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
 
@@ -598,6 +599,49 @@ function measurement_series(r::BatchRunner, first::Integer, n::Integer)
                 (Ptr{Cvoid}, Clonglong, Clonglong, Ptr{Cdouble}, Ptr{Clonglong}), r.h, first, n, out, counts))
     return [Measurement(counts[w], rows, out[1, :, :, w], out[2, :, :, w], out[3, :, :, w], out[4, :, :, w],
                         complex.(out[5:2:end, :, :, w], out[6:2:end, :, :, w])) for w in 1:n]
+end
+
+"""
+    set_measurement_fold!(runner; period=0, period_i=nothing)
+
+Fold the armed measurement's window onto one period (`acme_batch_set_measurement_fold`, synchronous averaging): slot
+`m mod period` of the window-relative sample `m` accumulates y, per instance and measured row.  `period` samples for every
+instance, or `period_i::Vector{Int64}`, one period per instance (1 ... 65536).  Needs an armed measurement that has not been
+fed yet; not together with a series.
+"""
+function set_measurement_fold!(r::BatchRunner; period::Integer=0, period_i=nothing)
+    r.meas === nothing && error("no measurement is armed")
+    per = period_i === nothing ? Int64[] : convert(Vector{Int64}, period_i)
+    period_i === nothing || length(per) == r.n || throw(DimensionMismatch("period_i needs one entry per instance ($(r.n))"))
+    GC.@preserve per check(ccall((:acme_batch_set_measurement_fold, lib), Cint, (Ptr{Cvoid}, Clonglong, Ptr{Clonglong}),
+                r.h, period, ptr_or_null(per)))
+    return r
+end
+
+"""
+    measurement_fold(runner; sums=false) -> (mean, period, count)
+
+The fold so far (`acme_batch_get_measurement_fold`): `mean` is Pmax x nrows x N, slot `s` (1-based) of instance `i` the mean of
+the window's samples `m` with `m mod period[i] == s - 1`; slots no sample has reached, and those beyond `period[i]`, are NaN.
+`sums=true`: `mean` holds the slots' sums, undivided (`acme_batch_get_measurement_fold_sums`).
+"""
+function measurement_fold(r::BatchRunner; sums::Bool=false)
+    spec = r.meas
+    spec === nothing && error("no measurement is armed")
+    ny = ACME.ny(r.model)
+    nrows = spec.rows == 0 ? min(ny, 64) : count_ones(spec.rows)
+    period = Vector{Clonglong}(undef, r.n)
+    count = Ref{Clonglong}(0)
+    check(ccall((:acme_batch_get_measurement_fold, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Clonglong}, Ptr{Clonglong}),
+                r.h, C_NULL, period, count))
+    mean = Array{Float64,3}(undef, maximum(period; init=0), nrows, r.n)     # the ABI's [N][nrows][Pmax]
+    if sums
+        check(ccall((:acme_batch_get_measurement_fold_sums, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), r.h, mean))
+    else
+        check(ccall((:acme_batch_get_measurement_fold, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Clonglong}, Ptr{Clonglong}),
+                    r.h, mean, C_NULL, C_NULL))
+    end
+    return (mean=mean, period=period, count=count[])
 end
 
 """
