@@ -1866,8 +1866,8 @@ static int src_commit(acme_batch *b) {
     if (!S.armed) S.clock = 0;
     return ACME_OK;
 }
-// kind, den (SINE, MULTISINE: f_den; TABLE: P), the arrays of the kind (host arrays of N entries, w of P; NULL = default;
-// MULTISINE: f_num, phase and amp hold tones x N entries)
+// kind, den (SINE, MULTISINE: f_den; TABLE: P; NOISE: hold), the arrays of the kind (host arrays of N entries, w of P; NULL =
+// default; MULTISINE: f_num, phase and amp hold tones x N entries; NOISE: f_num holds the streams, tones the distribution)
 static int set_source(acme_batch *b, int row, int kind, long long den, const long long *f_num, const long long *phase,
                       const double *w, const double *amp, const double *offset, int tones = 1) {
     join_worker(b);
@@ -1900,6 +1900,10 @@ static int set_source(acme_batch *b, int row, int kind, long long den, const lon
         if (den < 1 || den > SRC_MAX_TABLE) return fail(ACME_ERR_INVALID, "table source: P must be 1 ... 2^24");
         if (!w) return fail(ACME_ERR_INVALID, "table source: null table");
     }
+    if (kind == SRC_NOISE) {
+        if (tones != SRC_UNIFORM && tones != SRC_GAUSSIAN) return fail(ACME_ERR_INVALID, "noise source: dist must be ACME_NOISE_UNIFORM or ACME_NOISE_GAUSSIAN");
+        if (den < 1 || den >= (1ll << 31)) return fail(ACME_ERR_INVALID, "noise source: hold must be 1 ... 2^31 - 1");
+    }
     const double *amp_n = kind == SRC_MULTISINE ? nullptr : amp;       // (MULTISINE: tones x N amplitudes, checked with their tones above)
     for (size_t i = 0; i < N; ++i)
         if ((amp_n && !std::isfinite(amp_n[i])) || (offset && !std::isfinite(offset[i])))
@@ -1912,12 +1916,12 @@ static int set_source(acme_batch *b, int row, int kind, long long den, const lon
     SrcRow R{};
     R.kind = kind;
     R.den = kind == SRC_CONST ? 1 : den;
-    R.tones = kind == SRC_MULTISINE ? tones : 0;
+    R.tones = kind == SRC_MULTISINE || kind == SRC_NOISE ? tones : 0;
     const size_t NT = kind == SRC_MULTISINE ? N * (size_t)tones : N;
     const bool sine = kind == SRC_SINE || kind == SRC_MULTISINE;
     int rc = src_upload(offset, sizeof(double) * N, (const void **)&R.off);
     if (rc == ACME_OK && kind != SRC_CONST) rc = src_upload(amp, sizeof(double) * NT, (const void **)&R.amp);
-    if (rc == ACME_OK && sine) rc = src_upload(f_num, sizeof(long long) * NT, (const void **)&R.fnum);
+    if (rc == ACME_OK && (sine || kind == SRC_NOISE)) rc = src_upload(f_num, sizeof(long long) * NT, (const void **)&R.fnum);
     if (rc == ACME_OK && sine) rc = src_upload(phase, sizeof(long long) * NT, (const void **)&R.phase);
     if (rc == ACME_OK && kind == SRC_TABLE) rc = src_upload(w, sizeof(double) * (size_t)den, (const void **)&R.w);
     for (auto &e : b->os.ev) if (rc == ACME_OK && !e && be::event_create(&e) != 0) rc = fail(ACME_ERR_HIP, "hipEventCreate");      // (the host pipeline of run_os)
@@ -1950,6 +1954,11 @@ int acme_batch_set_source_table(acme_batch *b, int row, const double *w, long lo
 int acme_batch_set_source_multisine(acme_batch *b, int row, long long f_den, int tones, long long *f_num, long long *phase,
                                     const double *amp, const double *offset) {
     return set_source(b, row, SRC_MULTISINE, f_den, f_num, phase, nullptr, amp, offset, tones);
+}
+
+int acme_batch_set_source_noise(acme_batch *b, int row, int dist, long long hold, long long *stream, const double *amp,
+                                const double *offset) {
+    return set_source(b, row, SRC_NOISE, hold, stream, nullptr, nullptr, amp, offset, dist);
 }
 
 int acme_batch_clear_source(acme_batch *b, int row) {

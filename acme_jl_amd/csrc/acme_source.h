@@ -9,6 +9,12 @@
 //   MULTISINE  a sum of 1 ... SRC_MAX_TONES sines as ONE chain in tone order: v = offset_i, then v = fma(amp_ki, sin(th_k), v)
 //           for k = 0 ... tones - 1, each th_k reduced and formed as SINE's from f_num_ki, phase_ki (per-tone arrays [tones][N]);
 //           one tone is the SINE row bit for bit
+//   NOISE   counter based: one Philox4x32-10 block per (instance, row, q = n div hold) -- counter (q mod 2^32, q div 2^32,
+//           row, 0), key (stream_i mod 2^32, stream_i div 2^32) -- gives r0 ... r3 and the 53-bit draw
+//           x = r0 + 2^32 (r1 mod 2^21);
+//           UNIFORM   fma(amp_i, U, offset_i),  U = (2 x + 1 - 2^53) 2^-53 (exact, odd: in (-1, 1), never 0)
+//           GAUSSIAN  fma(amp_i, g, offset_i),  g = sqrt(-2 log(u1)) sin(th),  u1 = (x + 1) 2^-53,  th = phase_angle(r2, 2^32)
+//           a sample depends on (stream_i, row, q) alone: never on the slice, tile, thread or call that computes it
 //
 // One launch per time slice (acme_api.inc run_os, where the expand kernel sits for constant rows) writes the slice's full
 // [N][len][nu] block: sourced rows generated, the others gathered from the caller's rows.
@@ -24,7 +30,11 @@
 // instance) is staged in LDS once per block while the rows' windows fit SRC_LDS doubles; rows beyond that read w from
 // HBM / L2.  A MULTISINE row keeps one kappa and one step PER TONE (the same two reductions per tone and instance, the same
 // conditional subtraction per tone and sample); a launch with such a row takes the kernel's second instantiation
-// (src_thread<true>, acme_source_multi_kernel: src_plan decides), every other launch the one it always took.
+// (src_thread<SRC_MODE_MULTI>, acme_source_multi_kernel: src_plan decides), a launch with a NOISE row the third
+// (src_thread<SRC_MODE_NOISE>, acme_source_noise_kernel: the first kernel's kinds and NOISE), a launch with NOISE and MULTISINE
+// rows the fourth (src_thread<SRC_MODE_NOISE_MULTI>, acme_source_noise_multi_kernel), every other launch the one it always
+// took.  A NOISE row keeps q and n mod hold of the thread's first sample (the row's and the thread's alone) and steps
+// them by dt div hold, dt mod hold with one conditional carry: no division per sample; only the key is the instance's.
 //
 // The per-thread functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops over (block, thread) otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with
@@ -39,7 +49,11 @@
 
 namespace acme {
 
-constexpr int SRC_NONE = 0, SRC_CONST = 1, SRC_SINE = 2, SRC_TABLE = 3, SRC_MULTISINE = 4;     // (include/acme_hip.h: ACME_SOURCE_*)
+constexpr int SRC_NONE = 0, SRC_CONST = 1, SRC_SINE = 2, SRC_TABLE = 3, SRC_MULTISINE = 4, SRC_NOISE = 5;      // (include/acme_hip.h: ACME_SOURCE_*)
+constexpr int SRC_UNIFORM = 0, SRC_GAUSSIAN = 1;    // a NOISE row's distribution (ACME_NOISE_*)
+// the source kernel's instantiations (src_plan): bit 0: the launch may hold MULTISINE rows; bit 1: NOISE rows
+constexpr int SRC_MODE_PLAIN = 0, SRC_MODE_MULTI = 1, SRC_MODE_NOISE = 2, SRC_MODE_NOISE_MULTI = 3;
+constexpr double SRC_2M53 = 1.0 / 9007199254740992.0;      // 2^-53: the scale of a NOISE row's 53-bit draw
 constexpr int SRC_MAX_TONES = 4;            // tones of a MULTISINE row (ACME_MAX_SOURCE_TONES)
 constexpr long long SRC_MAX_TABLE = 1ll << 24;
 constexpr int SRC_BLOCK = 256;              // threads per block
@@ -51,11 +65,11 @@ constexpr int SRC_LDS = 4096;               // doubles of LDS for the table rows
 struct SrcRow {
     int kind;                   // SRC_*; SRC_NONE: the caller's row
     int var;                    // SRC_NONE: the row's place among the caller's rows
-    long long den;              // SINE, MULTISINE: f_den; TABLE: P
+    long long den;              // SINE, MULTISINE: f_den; TABLE: P; NOISE: hold
     const double *amp, *off;    // default 1, 0
-    const long long *fnum, *phase;      // default 0, 0
+    const long long *fnum, *phase;      // default 0, 0; NOISE: fnum holds the streams (default: stream_i = i)
     const double *w;            // TABLE: [P]
-    int tones;                  // MULTISINE: amp, fnum, phase are [tones][n] (tone k of instance i at [k * n + i])
+    int tones;                  // MULTISINE: amp, fnum, phase are [tones][n] (tone k of instance i at [k * n + i]); NOISE: SRC_UNIFORM / _GAUSSIAN
 };
 
 struct SrcArgs {
@@ -67,7 +81,7 @@ struct SrcArgs {
     int nu, nin;
     int vec;                    // 16-byte stores: nu even, or nu = 1 with len and dpitch even; dst 16-byte aligned
     unsigned long long lds_rows;        // the table rows whose windows are staged in LDS
-    int multi;                  // a row is MULTISINE: the launch takes the multi-tone instantiation
+    int mode;                   // SRC_MODE_*: the instantiation the launch takes (src_plan)
 };
 
 struct alignas(16) SrcPair { double a, b; };
@@ -121,18 +135,59 @@ struct SrcRunMulti : SrcRun {
     double ampx[SRC_MAX_TONES - 1];
     unsigned long long kx[SRC_MAX_TONES - 1], stepx[SRC_MAX_TONES - 1];
 };
-template <bool MT> struct SrcRunOf { typedef SrcRun type; };
-template <> struct SrcRunOf<true> { typedef SrcRunMulti type; };
+// a NOISE row beside those: the row's counter at the thread's first sample and its step (n mod hold and dt mod hold live in
+// m0 and dstep above, hold in den) ...
+struct SrcSlotNoise : SrcSlot {
+    unsigned long long q0, dq;  // (n0 + first sample) div hold; dt div hold
+    unsigned int row;           // the counter's third word
+};
+// ... and the instance's key; the running counter (n mod hold runs in k above); Base: SrcRun, or SrcRunMulti in a launch that
+// holds MULTISINE rows too
+template <class Base> struct SrcRunNoise : Base {
+    unsigned long long q;
+    unsigned int key0, key1;
+};
+template <int MODE> struct SrcRunOf { typedef SrcRun type; };
+template <> struct SrcRunOf<SRC_MODE_MULTI> { typedef SrcRunMulti type; };
+template <> struct SrcRunOf<SRC_MODE_NOISE> { typedef SrcRunNoise<SrcRun> type; };
+template <> struct SrcRunOf<SRC_MODE_NOISE_MULTI> { typedef SrcRunNoise<SrcRunMulti> type; };
+template <int MODE> struct SrcSlotOf { typedef SrcSlot type; };
+template <> struct SrcSlotOf<SRC_MODE_NOISE> { typedef SrcSlotNoise type; };
+template <> struct SrcSlotOf<SRC_MODE_NOISE_MULTI> { typedef SrcSlotNoise type; };
 
-// row `row`, first sample tb + ts of the slice, dt samples per step (MT: the launch may hold MULTISINE rows)
-template <bool MT>
+// Philox4x32-10 (Salmon et al., SC'11; the Random123 constants): counter c, key k -> four words
+struct SrcWords { unsigned int r0, r1, r2, r3; };
+ACME_HD inline SrcWords src_philox(unsigned int c0, unsigned int c1, unsigned int c2, unsigned int c3, unsigned int k0, unsigned int k1) {
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c1 ^ k0, n2 = (unsigned int)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (unsigned int)p1; c3 = (unsigned int)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    return SrcWords{c0, c1, c2, c3};
+}
+// a NOISE row's draw from its block's words, before amp and offset: U or g (the operations in exactly this order)
+ACME_HD inline double src_noise_draw(const SrcWords &w, int dist) {
+    const unsigned long long x = (unsigned long long)w.r0 + ((unsigned long long)(w.r1 & 0x1FFFFFu) << 32);       // 53 bits
+    if (dist == SRC_UNIFORM) return (double)((long long)(2ull * x + 1ull) - (1ll << 53)) * SRC_2M53;       // (an odd integer below 2^53: exact)
+    const double u1 = (double)(x + 1ull) * SRC_2M53;         // (0, 1], exact
+    const double th = phase_angle((long long)w.r2, 1ll << 32);
+    const double rad = sqrt(-2.0 * log(u1));
+    return rad * sin(th);
+}
+
+// row `row`, first sample tb + ts of the slice, dt samples per step (MODE: the launch may hold MULTISINE rows)
+template <int MODE>
 ACME_HD inline void src_slot_init(const SrcArgs &A, int row, long long tb, long long tl, long long ts, long long dt, const double *lds,
                                   SrcSlot &S) {
     const SrcRow &R = A.rows[row];
     S.kind = R.kind; S.var = R.var; S.tones = R.tones;
     S.amp = R.amp; S.off = R.off; S.fnum = R.fnum; S.phase = R.phase; S.tab = R.w;
     S.den = 1; S.m0 = 0; S.dstep = 0;
-    if (R.kind == SRC_SINE || (MT && R.kind == SRC_MULTISINE)) {
+    if (R.kind == SRC_SINE || ((MODE & SRC_MODE_MULTI) && R.kind == SRC_MULTISINE)) {
         S.den = (unsigned long long)R.den;
         S.m0 = ((unsigned long long)(A.n0 % R.den) + (unsigned long long)(tb + ts)) % S.den;      // (n mod f_den first)
         S.dstep = (unsigned long long)dt % S.den;
@@ -147,6 +202,19 @@ ACME_HD inline void src_slot_init(const SrcArgs &A, int row, long long tb, long 
         }
         S.dstep = (unsigned long long)dt % S.den;
     }
+}
+
+// ... of a launch that may hold NOISE rows: the counter and n mod hold of the thread's first sample, their steps
+template <int MODE>
+ACME_HD inline void src_slot_init(const SrcArgs &A, int row, long long tb, long long tl, long long ts, long long dt, const double *lds,
+                                  SrcSlotNoise &S) {
+    src_slot_init<MODE>(A, row, tb, tl, ts, dt, lds, static_cast<SrcSlot &>(S));
+    S.q0 = 0ull; S.dq = 0ull; S.row = (unsigned int)row;
+    if (S.kind != SRC_NOISE) return;
+    const unsigned long long hold = (unsigned long long)A.rows[row].den, n = (unsigned long long)A.n0 + (unsigned long long)(tb + ts);
+    S.den = hold;
+    S.q0 = n / hold; S.m0 = n % hold;
+    S.dq = (unsigned long long)dt / hold; S.dstep = (unsigned long long)dt % hold;
 }
 
 ACME_HD inline void src_run_init(const SrcArgs &A, const SrcSlot &S, long long i, long long tb, long long ts, SrcRun &R) {
@@ -184,6 +252,16 @@ ACME_HD inline void src_run_init(const SrcArgs &A, const SrcSlot &S, long long i
     }
 }
 
+// ... of a launch that may hold NOISE rows: the instance's key (src_run_init above has set k = n mod hold, step = dt mod hold)
+template <class Base>
+ACME_HD inline void src_run_init(const SrcArgs &A, const SrcSlotNoise &S, long long i, long long tb, long long ts, SrcRunNoise<Base> &R) {
+    src_run_init(A, static_cast<const SrcSlot &>(S), i, tb, ts, static_cast<Base &>(R));
+    R.q = S.q0; R.key0 = 0u; R.key1 = 0u;
+    if (S.kind != SRC_NOISE) return;
+    const unsigned long long stream = S.fnum ? (unsigned long long)S.fnum[i] : (unsigned long long)i;
+    R.key0 = (unsigned int)stream; R.key1 = (unsigned int)(stream >> 32);
+}
+
 // the row's value at the thread's current sample; on to the next (dt samples later)
 ACME_HD inline double src_next(const SrcSlot &S, SrcRun &R, long long ustep) {
     double v;
@@ -218,9 +296,20 @@ ACME_HD inline double src_next(const SrcSlot &S, SrcRunMulti &R, long long ustep
     }
     return v;
 }
+// ... of a launch that may hold NOISE rows: the block of the sample's counter
+template <class Base>
+ACME_HD inline double src_next(const SrcSlotNoise &S, SrcRunNoise<Base> &R, long long ustep) {
+    if (S.kind != SRC_NOISE) return src_next(static_cast<const SrcSlot &>(S), static_cast<Base &>(R), ustep);
+    const SrcWords w = src_philox((unsigned int)R.q, (unsigned int)(R.q >> 32), S.row, 0u, R.key0, R.key1);
+    const double v = fma(R.amp, src_noise_draw(w, S.tones), R.off);
+    R.k += R.step;
+    R.q += S.dq;
+    if (R.k >= S.den) { R.k -= S.den; ++R.q; }
+    return v;
+}
 
 // thread tid of block (bx, by): instances bx SRC_INST ..., samples by SRC_TILE ...
-template <bool MT>
+template <int MODE>
 ACME_HD inline void src_thread(const SrcArgs &A, long long bx, long long by, int tid, const double *lds) {
     const int nu = A.nu;
     const long long tb = by * SRC_TILE, tl = A.len - tb < SRC_TILE ? A.len - tb : SRC_TILE;
@@ -237,13 +326,14 @@ ACME_HD inline void src_thread(const SrcArgs &A, long long bx, long long by, int
         ts = ts1 = tid / per;
         dt = act / per;
     }
-    SrcSlot s0, s1;
-    if (MT) s1 = SrcSlot{};         // (read by src_run_init's tone loop only when A.vec has filled it)
-    src_slot_init<MT>(A, r0, tb, tl, ts, dt, lds, s0);
-    if (A.vec) src_slot_init<MT>(A, r1, tb, tl, ts1, dt, lds, s1);
+    typedef typename SrcSlotOf<MODE>::type Slot;
+    Slot s0, s1;
+    if (MODE != SRC_MODE_PLAIN) s1 = Slot{};        // (read by src_run_init's tone loop only when A.vec has filled it)
+    src_slot_init<MODE>(A, r0, tb, tl, ts, dt, lds, s0);
+    if (A.vec) src_slot_init<MODE>(A, r1, tb, tl, ts1, dt, lds, s1);
     const long long ustep = dt * A.nin;
     for (long long i = bx * SRC_INST; i < (bx + 1) * SRC_INST && i < A.n; ++i) {
-        typename SrcRunOf<MT>::type q0, q1;
+        typename SrcRunOf<MODE>::type q0, q1;
         src_run_init(A, s0, i, tb, ts, q0);
         double *d = A.dst + (i * A.dpitch + tb) * nu;
         if (A.vec) {
@@ -264,9 +354,9 @@ inline void src_plan(SrcArgs &A, const SrcRow *host_rows, bool use_lds) {
     const long long tmax = A.len < SRC_TILE ? A.len : SRC_TILE;
     long long used = 0;
     A.lds_rows = 0ull;
-    A.multi = 0;
+    A.mode = SRC_MODE_PLAIN;
     for (int r = 0; r < A.nu; ++r)
-        if (host_rows[r].kind == SRC_MULTISINE) A.multi = 1;
+        A.mode |= host_rows[r].kind == SRC_MULTISINE ? SRC_MODE_MULTI : host_rows[r].kind == SRC_NOISE ? SRC_MODE_NOISE : 0;
     for (int r = 0; r < A.nu && use_lds; ++r) {
         if (host_rows[r].kind != SRC_TABLE) continue;
         const long long win = host_rows[r].den < tmax ? host_rows[r].den : tmax;
@@ -295,7 +385,7 @@ __global__ __launch_bounds__(acme::SRC_BLOCK) void acme_source_kernel(acme::SrcA
         acme::src_stage(A, blockIdx.y, threadIdx.x, lds);
         __syncthreads();
     }
-    acme::src_thread<false>(A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+    acme::src_thread<acme::SRC_MODE_PLAIN>(A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
 }
 __global__ __launch_bounds__(acme::SRC_BLOCK) void acme_source_multi_kernel(acme::SrcArgs A) {
     __shared__ double lds[acme::SRC_LDS];
@@ -303,7 +393,25 @@ __global__ __launch_bounds__(acme::SRC_BLOCK) void acme_source_multi_kernel(acme
         acme::src_stage(A, blockIdx.y, threadIdx.x, lds);
         __syncthreads();
     }
-    acme::src_thread<true>(A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+    acme::src_thread<acme::SRC_MODE_MULTI>(A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+__global__ __launch_bounds__(acme::SRC_BLOCK) void acme_source_noise_kernel(acme::SrcArgs A) {
+    __shared__ double lds[acme::SRC_LDS];
+    if (A.lds_rows) {           // (uniform over the launch; NOISE rows use no LDS)
+        acme::src_stage(A, blockIdx.y, threadIdx.x, lds);
+        __syncthreads();
+    }
+    acme::src_thread<acme::SRC_MODE_NOISE>(A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+// (two waves per SIMD: the rows' tones and counters together would take 290 registers, 34 of them accumulation registers;
+// bounded to 256 the allocator parks 54 in scratch instead -- DESIGN 2.5i)
+__global__ __launch_bounds__(acme::SRC_BLOCK, 2) void acme_source_noise_multi_kernel(acme::SrcArgs A) {
+    __shared__ double lds[acme::SRC_LDS];
+    if (A.lds_rows) {           // (uniform over the launch)
+        acme::src_stage(A, blockIdx.y, threadIdx.x, lds);
+        __syncthreads();
+    }
+    acme::src_thread<acme::SRC_MODE_NOISE_MULTI>(A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
 }
 __global__ __launch_bounds__(256) void acme_source_copy_kernel(acme::SrcCopyArgs A) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -312,7 +420,9 @@ __global__ __launch_bounds__(256) void acme_source_copy_kernel(acme::SrcCopyArgs
 namespace acme {
 inline int src_launch(const SrcArgs &A, hipStream_t st) {
     const dim3 grid((unsigned)((A.n + SRC_INST - 1) / SRC_INST), (unsigned)((A.len + SRC_TILE - 1) / SRC_TILE));
-    if (A.multi) hipLaunchKernelGGL(acme_source_multi_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
+    if (A.mode == SRC_MODE_NOISE_MULTI) hipLaunchKernelGGL(acme_source_noise_multi_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
+    else if (A.mode == SRC_MODE_NOISE) hipLaunchKernelGGL(acme_source_noise_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
+    else if (A.mode == SRC_MODE_MULTI) hipLaunchKernelGGL(acme_source_multi_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
     else hipLaunchKernelGGL(acme_source_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
     return (int)hipGetLastError();
 }
@@ -329,8 +439,10 @@ inline int src_launch(const SrcArgs &A, void *) {
         for (int tid = 0; tid < SRC_BLOCK && A.lds_rows; ++tid) src_stage(A, by, tid, lds.data());
         for (long long bx = 0; bx * SRC_INST < A.n; ++bx)
             for (int tid = 0; tid < SRC_BLOCK; ++tid) {
-                if (A.multi) src_thread<true>(A, bx, by, tid, lds.data());
-                else src_thread<false>(A, bx, by, tid, lds.data());
+                if (A.mode == SRC_MODE_NOISE_MULTI) src_thread<SRC_MODE_NOISE_MULTI>(A, bx, by, tid, lds.data());
+                else if (A.mode == SRC_MODE_NOISE) src_thread<SRC_MODE_NOISE>(A, bx, by, tid, lds.data());
+                else if (A.mode == SRC_MODE_MULTI) src_thread<SRC_MODE_MULTI>(A, bx, by, tid, lds.data());
+                else src_thread<SRC_MODE_PLAIN>(A, bx, by, tid, lds.data());
             }
     }
     return 0;

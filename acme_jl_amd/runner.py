@@ -64,16 +64,34 @@ ABI_SYMBOLS = [
     "acme_batch_set_source_const", "acme_batch_set_source_sine", "acme_batch_set_source_table", "acme_batch_clear_source",
     "acme_batch_set_source_clock", "acme_batch_get_source_clock", "acme_batch_run_sources", "acme_batch_run_sources_async",
     "acme_batch_render_sources",
-    "acme_batch_set_source_multisine", "acme_batch_set_measurement_bins",
+    "acme_batch_set_source_multisine", "acme_batch_set_source_noise", "acme_batch_set_measurement_bins",
     "acme_batch_set_measurement_series", "acme_batch_get_measurement_series",
     "acme_batch_set_measurement_fold", "acme_batch_get_measurement_fold", "acme_batch_get_measurement_fold_sums",
 ]
 
-SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE = 1, 2, 3, 4
+SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE, SOURCE_NOISE = 1, 2, 3, 4, 5
+NOISE_UNIFORM, NOISE_GAUSSIAN = 0, 1
 MAX_SOURCE_TONES = 4
 MAX_FOLD_PERIOD = 65536
-_SOURCE_KINDS = {"const": SOURCE_CONST, "sine": SOURCE_SINE, "table": SOURCE_TABLE, "multisine": SOURCE_MULTISINE,
-                 SOURCE_CONST: SOURCE_CONST, SOURCE_SINE: SOURCE_SINE, SOURCE_TABLE: SOURCE_TABLE, SOURCE_MULTISINE: SOURCE_MULTISINE}
+_SOURCE_KINDS = {"const": SOURCE_CONST, "sine": SOURCE_SINE, "table": SOURCE_TABLE, "multisine": SOURCE_MULTISINE, "noise": SOURCE_NOISE,
+                 SOURCE_CONST: SOURCE_CONST, SOURCE_SINE: SOURCE_SINE, SOURCE_TABLE: SOURCE_TABLE, SOURCE_MULTISINE: SOURCE_MULTISINE,
+                 SOURCE_NOISE: SOURCE_NOISE}
+_NOISE_DISTS = {"uniform": NOISE_UNIFORM, "gaussian": NOISE_GAUSSIAN, NOISE_UNIFORM: NOISE_UNIFORM, NOISE_GAUSSIAN: NOISE_GAUSSIAN}
+
+
+def noise_streams(n, stream=None, seed=0):
+    """The streams of a noise source over instances 0 ... n - 1 as the ABI takes them (int64; a stream is an unsigned 64-bit
+    value, so 2^63 ... 2^64 - 1 wrap to the negative integers): ``stream`` -- n integers -- or ``seed * 2^32 + i``"""
+    if stream is None:
+        if not 0 <= int(seed) < 2 ** 31 or int(seed) != seed:
+            raise ValueError("a noise source's seed must be an integer 0 ... 2^31 - 1")
+        return (np.int64(int(seed)) << np.int64(32)) + np.arange(n, dtype=np.int64)
+    vals = [int(v) for v in np.asarray(stream, dtype=object).ravel()]
+    if len(vals) != n:
+        raise DimensionMismatch(f"a noise source's streams need {n} values")
+    if any(v != w for v, w in zip(vals, np.asarray(stream, dtype=object).ravel())) or not all(-2 ** 63 <= v < 2 ** 64 for v in vals):
+        raise DimensionMismatch("a noise source's streams must be 64-bit integers")
+    return np.array([v - 2 ** 64 if v >= 2 ** 63 else v for v in vals], dtype=np.int64)
 
 
 def _preload_torch_hip_runtime():
@@ -171,6 +189,7 @@ class Library:
         L.acme_batch_run_sources_async.argtypes = [vp, vp, vp, C.c_longlong, C.c_int, vp]
         L.acme_batch_render_sources.argtypes = [vp, vp, vp, C.c_longlong, C.c_int, vp]
         L.acme_batch_set_source_multisine.argtypes = [vp, C.c_int, C.c_longlong, C.c_int, lp, lp, dp, dp]
+        L.acme_batch_set_source_noise.argtypes = [vp, C.c_int, C.c_int, C.c_longlong, lp, dp, dp]
         L.acme_batch_set_measurement_bins.argtypes = [vp, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, lp, C.c_int, ip,
                                                       C.c_ulonglong]
         L.acme_batch_set_measurement_series.argtypes = [vp, C.c_longlong, C.c_longlong, C.c_longlong]
@@ -767,7 +786,8 @@ class ModelRunner:
             raise DimensionMismatch(f"{what} must be integers")
         return arr, arr.ctypes.data_as(C.POINTER(C.c_double if dtype is np.float64 else C.c_longlong)), src.shape[0]
 
-    def set_source(self, row, kind, amp=None, offset=None, f_den=None, f_num=None, phase=None, table=None):
+    def set_source(self, row, kind, amp=None, offset=None, f_den=None, f_num=None, phase=None, table=None,
+                   dist="gaussian", hold=1, stream=None, seed=0):
         """Give input row ``row`` a source (``acme_batch_set_source_*``): the library generates the row on the device, at
         source clock n (base-rate samples since the first source was armed) for instance i
 
@@ -778,14 +798,33 @@ class ModelRunner:
         * ``"multisine"``: a sum of 1 ... 4 sines, one fma chain in tone order from ``offset[i]``; ``f_num`` (required),
           ``phase``, ``amp``: (tones, N) or (tones,) -- per-instance tone frequencies, levels and relative phases (a two-tone
           intermodulation test); one tone is the ``"sine"`` row bit for bit
+        * ``"noise"``: ``fma(amp[i], d, offset[i])`` with d an independent, reproducible random draw per (stream[i], row,
+          n div hold) -- counter based (Philox4x32-10), so the value at clock n depends on nothing generated before, on no
+          call boundary and on no device.  ``dist="uniform"``: d in (-1, 1), never 0, variance 1/3; ``dist="gaussian"``: d
+          standard normal (Box-Muller, one draw per sample).  ``hold`` (1 ... 2^31 - 1): the draw is held over blocks of
+          ``hold`` samples aligned to the clock (1: white noise; larger: stepped random values, a jumping pot).  ``stream``:
+          N integers (equal streams on a row render equal sequences; the same stream on two rows independent ones);
+          otherwise ``stream[i] = seed * 2^32 + i`` with ``0 <= seed < 2^31``
 
         ``amp``, ``offset``, ``f_num``, ``phase``: None (amp 1, the others 0), a scalar or N values.  ``run_sources`` then runs
         without these rows; its results are those of ``run`` on ``render_sources``' array, bit for bit."""
         k = _SOURCE_KINDS.get(kind)
         if k is None:
-            raise ValueError(f"unknown source kind {kind!r}: 'const', 'sine', 'multisine' or 'table'")
+            raise ValueError(f"unknown source kind {kind!r}: 'const', 'sine', 'multisine', 'table' or 'noise'")
         oa, op = self._per_instance(offset, np.float64, "offset")
         L = self.lib.L
+        if k == SOURCE_NOISE:
+            d = _NOISE_DISTS.get(dist)
+            if d is None:
+                raise ValueError(f"unknown noise distribution {dist!r}: 'gaussian' or 'uniform'")
+            if int(hold) != hold:
+                raise ValueError("a noise source's hold must be an integer")
+            sa = noise_streams(self.n, stream, seed)
+            aa, ap = self._per_instance(amp, np.float64, "amp")
+            self.lib.check(L.acme_batch_set_source_noise(self.h, int(row), d, int(hold), sa.ctypes.data_as(C.POINTER(C.c_longlong)), ap, op))
+            self._sine.pop(int(row), None)
+            self._sources[int(row)] = k
+            return self
         if k == SOURCE_MULTISINE:
             if f_den is None or f_num is None:
                 raise ValueError("a multisine source needs f_den and f_num")
@@ -1335,9 +1374,12 @@ class MultiDeviceRunner:
         return self.run(u, y=False, check=check)
 
     # ---- sources: the per-instance parameters sliced over the devices ---------------------------
-    def set_source(self, row, kind, amp=None, offset=None, f_den=None, f_num=None, phase=None, table=None):
-        """``ModelRunner.set_source`` on every device's batch, each with its instances' parameters"""
+    def set_source(self, row, kind, amp=None, offset=None, f_den=None, f_num=None, phase=None, table=None,
+                   dist="gaussian", hold=1, stream=None, seed=0):
+        """``ModelRunner.set_source`` on every device's batch, each with its instances' parameters (a noise source's
+        streams are formed over the global instance index: a sharded batch renders what the single batch renders)"""
         multi = _SOURCE_KINDS.get(kind) == SOURCE_MULTISINE
+        streams = noise_streams(self.n, stream, seed) if _SOURCE_KINDS.get(kind) == SOURCE_NOISE else None
 
         def part(a, lo, hi):
             if multi and a is not None and np.ndim(a) == 2 and a is not offset:
@@ -1353,7 +1395,8 @@ class MultiDeviceRunner:
                 raise DimensionMismatch(f"per-instance source parameters need {self.n} values")
         for r, (lo, hi) in zip(self.runners, self.ranges):
             if r is not None:
-                r.set_source(row, kind, part(amp, lo, hi), part(offset, lo, hi), f_den, part(f_num, lo, hi), part(phase, lo, hi), table)
+                r.set_source(row, kind, part(amp, lo, hi), part(offset, lo, hi), f_den, part(f_num, lo, hi), part(phase, lo, hi), table,
+                             dist, hold, None if streams is None else streams[lo:hi], seed)
         return self
 
     def clear_source(self, row=-1):

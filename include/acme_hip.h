@@ -396,6 +396,21 @@ int acme_batch_get_measurement(acme_batch *b, double *out, long long *count);
  *                         SINE row bit for bit.  Per-instance tone frequencies, levels and relative phases: a two-tone
  *                         intermodulation sweep (the pair's centre, spacing, ratio) is one batch.  The per-tone arrays are
  *                         [tones][N]: tone k of instance i at [k * N + i]
+ *     ACME_SOURCE_NOISE   independent, reproducible random rows, COUNTER BASED: the value at clock n depends on (stream_i, row,
+ *                         q = n div hold) alone -- never on what was generated before, on the call boundaries or on the memory
+ *                         kind; a render at clock 2^62 costs what one at 0 costs.  One Philox4x32-10 block (multipliers
+ *                         D2511F53, CD9E8D57; key increments 9E3779B9, BB67AE85) per (instance, row, q): counter (q mod 2^32,
+ *                         q div 2^32, row, 0), key (stream_i mod 2^32, stream_i div 2^32) with stream_i read as unsigned 64 bit,
+ *                         outputs r0 ... r3; the 53-bit draw x = r0 + 2^32 (r1 mod 2^21), then
+ *                           ACME_NOISE_UNIFORM   fma(amp_i, U, offset_i), U = (2 x + 1 - 2^53) 2^-53: exact, symmetric about 0,
+ *                                                never 0, in (-1, 1); variance 1/3
+ *                           ACME_NOISE_GAUSSIAN  fma(amp_i, g, offset_i), g = sqrt(-2 log(u1)) sin(th), u1 = (x + 1) 2^-53 in
+ *                                                (0, 1], th = 2 pi kappa / 2^32 with kappa = r2 taken to (-2^31, 2^31] (the SINE
+ *                                                row's angle); variance 1
+ *                         hold (1 ... 2^31 - 1): the row is a sample-and-hold of the draw over blocks of `hold` samples aligned
+ *                         to the CLOCK (1: white noise at the base rate; larger: stepped random values, a jumping pot).
+ *                         stream: a HOST array of N entries or NULL (stream_i = i); equal streams on one row render equal
+ *                         sequences, the same stream on two rows independent ones
  *   parameters    amp, offset, f_num, phase: HOST arrays of N entries, copied to the device by the call (parameters, not
  *                 signals); NULL = the same default for every instance (amp 1, the others 0).  w: a host array of P entries.
  *                 (f_num and phase are only read.)
@@ -415,6 +430,9 @@ int acme_batch_get_measurement(acme_batch *b, double *out, long long *count);
 #define ACME_SOURCE_SINE 2
 #define ACME_SOURCE_TABLE 3
 #define ACME_SOURCE_MULTISINE 4
+#define ACME_SOURCE_NOISE 5
+#define ACME_NOISE_UNIFORM 0
+#define ACME_NOISE_GAUSSIAN 1
 #define ACME_MAX_SOURCE_TABLE 16777216
 #define ACME_MAX_SOURCE_TONES 4
 /* give input row `row` a source (replacing the one it has).  Validates its arguments (ACME_ERR_INVALID: row beyond the model's
@@ -429,6 +447,10 @@ int acme_batch_set_source_table(acme_batch *b, int row, const double *w, long lo
  * and a null f_num; an f_num or phase out of range is named by tone and instance. */
 int acme_batch_set_source_multisine(acme_batch *b, int row, long long f_den, int tones, long long *f_num, long long *phase,
                                     const double *amp, const double *offset);
+/* stream: [N] or NULL (stream_i = i), only read; amp, offset: [N] or NULL.  ACME_ERR_INVALID also for a dist that is neither
+ * ACME_NOISE_UNIFORM nor ACME_NOISE_GAUSSIAN and a hold outside 1 ... 2^31 - 1. */
+int acme_batch_set_source_noise(acme_batch *b, int row, int dist, long long hold, long long *stream, const double *amp,
+                                const double *offset);
 /* the row is the caller's again; row < 0: every row.  With the last source the clock goes (the next first source starts
  * it at 0). */
 int acme_batch_clear_source(acme_batch *b, int row);

@@ -37,7 +37,7 @@ import ACME: run!, solve, hasconverged, needediterations, set_resabstol!,
 export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host_buffers!, release_host_buffers!, set_isolation!, set_balance!,
        MeasureSpec, Measurement, set_measurement!, clear_measurement!, reset_measurement!, measurement, measurement_plan, measure!,
        set_source!, clear_source!, source_clock, source_clock!, run_sources!, render_sources,
-       set_source_multisine!, set_measurement_bins!, set_measurement_series!, measurement_series,
+       set_source_multisine!, set_source_noise!, set_measurement_bins!, set_measurement_series!, measurement_series,
        set_measurement_fold!, measurement_fold
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
@@ -52,6 +52,8 @@ const ACME_MAX_OVERSAMPLING = 16
 const ACME_MAX_HARMONICS = 32
 const ACME_MAX_SERIES_WINDOWS = 1048576
 const ACME_SOURCE_CONST, ACME_SOURCE_SINE, ACME_SOURCE_TABLE, ACME_SOURCE_MULTISINE = Cint(1), Cint(2), Cint(3), Cint(4)
+const ACME_SOURCE_NOISE = Cint(5)
+const ACME_NOISE_UNIFORM, ACME_NOISE_GAUSSIAN = Cint(0), Cint(1)
 const ACME_MAX_SOURCE_TABLE = 16777216
 const ACME_MAX_SOURCE_TONES = 4
 const KIND_NQ = Dict(1 => 2, 2 => 4, 3 => 5, 4 => 3, 5 => 2, 6 => 4)
@@ -724,6 +726,26 @@ function set_source_multisine!(r::BatchRunner, row::Integer, f_den::Integer, f_n
     GC.@preserve f_num p a o check(ccall((:acme_batch_set_source_multisine, lib), Cint,
                 (Ptr{Cvoid}, Cint, Clonglong, Cint, Ptr{Clonglong}, Ptr{Clonglong}, Ptr{Cdouble}, Ptr{Cdouble}),
                 r.h, row - 1, f_den, tones, f_num, ptr_or_null(p), ptr_or_null(a), ptr_or_null(o)))
+    push!(r.sources, Int(row))
+    return r
+end
+
+"""
+    set_source_noise!(runner, row; dist=:gaussian, hold=1, stream=nothing, amp=nothing, offset=nothing)
+
+Give input row `row` (1-based) a noise source (`acme_batch_set_source_noise`): `fma(amp[i], d, offset[i])` with d an
+independent, reproducible random draw per (stream[i], row, n div hold) -- counter based (Philox4x32-10), so the value at source
+clock n depends on nothing generated before, on no call boundary and on no device.  `dist = :uniform`: d in (-1, 1), never 0,
+variance 1/3; `dist = :gaussian`: d standard normal (Box-Muller, one draw per sample).  `hold` (1 ... 2^31 - 1): the draw is
+held over blocks of `hold` samples aligned to the clock.  `stream`: N `Int64` (read as unsigned 64-bit values), or `nothing`:
+instance i (0-based) takes stream i.  `amp`, `offset` as for `set_source!`.
+"""
+function set_source_noise!(r::BatchRunner, row::Integer; dist::Symbol=:gaussian, hold::Integer=1, stream=nothing, amp=nothing, offset=nothing)
+    d = dist === :gaussian ? ACME_NOISE_GAUSSIAN : dist === :uniform ? ACME_NOISE_UNIFORM : error("unknown noise distribution $dist: :gaussian or :uniform")
+    s, a, o = perinstance(Clonglong, stream, r.n), perinstance(Cdouble, amp, r.n), perinstance(Cdouble, offset, r.n)
+    GC.@preserve s a o check(ccall((:acme_batch_set_source_noise, lib), Cint,
+                (Ptr{Cvoid}, Cint, Cint, Clonglong, Ptr{Clonglong}, Ptr{Cdouble}, Ptr{Cdouble}),
+                r.h, row - 1, d, hold, ptr_or_null(s), ptr_or_null(a), ptr_or_null(o)))
     push!(r.sources, Int(row))
     return r
 end
