@@ -191,6 +191,36 @@ struct acme_batch {
 static void join_worker(acme_batch *b) {
     if (b && b->worker.joinable()) b->worker.join();
 }
+// The prologue of everything that runs a batch: join its worker (NULL: the caller is the worker), then hold the backend's
+// run mutex, if it has one, to the end of the call -- the CPU emulator backend is not re-entrant, and a worker of
+// ANOTHER batch may be running.
+struct RunGuard {
+    std::unique_lock<std::mutex> serial;
+    explicit RunGuard(acme_batch *join) {
+        join_worker(join);
+        if (std::mutex *m = be::run_mutex()) serial = std::unique_lock<std::mutex>(*m);
+    }
+};
+// start `run` (-> status) on the batch's worker thread (acme_batch_run_async; the worker has been joined)
+template <class Run>
+static int start_worker(acme_batch *b, Run run) {
+    if (b->worker_rc != ACME_OK) {       // a failed asynchronous run nobody waited for: reported now, not dropped
+        const int rc = b->worker_rc;
+        b->worker_rc = ACME_OK;
+        return fail(rc, "previous asynchronous run failed: " + b->worker_err);
+    }
+    b->worker_err.clear();
+    try {
+        b->worker = std::thread([b, run]() {
+            RunGuard serial(nullptr);    // (the synchronous entry points join b->worker first: not from the worker itself)
+            b->worker_rc = run();
+            if (b->worker_rc != ACME_OK) b->worker_err = g_err;      // the worker's thread-local message
+        });
+    } catch (const std::exception &e) {
+        return fail(ACME_ERR_HIP, std::string("cannot start the worker thread: ") + e.what());
+    }
+    return ACME_OK;
+}
 
 // free the per-instance parameters of input row `row`'s source (row < 0: of every row) and mark the row as the caller's
 static void src_release(acme_batch *b, int row) {
@@ -1146,31 +1176,42 @@ static void fill_gargs(const acme_batch *b, GArgs &A) {
     A.mode = GEN_RUN;
 }
 
+// The event ring around the launches: ev_take retires the oldest pair when the ring is full and records the start event
+// of the next slot on `st`; ev_commit records its end event behind the launches and counts the launch's T samples.
+static int ev_take(acme_batch *b, be::stream_t st, int *slot) {
+    if (b->ev_pending == acme_batch::NEV) {
+        int rc_ = drain_events(b, 1);
+        if (rc_ != ACME_OK) return rc_;
+    }
+    *slot = (b->ev_head + b->ev_pending) % acme_batch::NEV;
+    HIPCHK(be::event_record(b->ev0[*slot], st));
+    return ACME_OK;
+}
+static int ev_commit(acme_batch *b, be::stream_t st, int slot, long long T, int *slot_out) {
+    HIPCHK(be::event_record(b->ev1[slot], st));
+    ++b->ev_pending;
+    b->samples_done += T;
+    if (slot_out) *slot_out = slot;
+    return ACME_OK;
+}
+
 static int launch_run(acme_batch *b, const double *du, double *dy, long long T, be::stream_t st, int *slot_out,
                       long long u_stride = 0, long long y_stride = 0, const long long *u_ready = nullptr) {
+    int slot = 0, rc_;
     if (b->generic) {
         GArgs A{};
         fill_gargs(b, A);
         A.u = du;
         A.y = dy;
         A.T = T;
-        if (b->ev_pending == acme_batch::NEV) {
-            int rc_ = drain_events(b, 1);
-            if (rc_ != ACME_OK) return rc_;
-        }
-        const int slot = (b->ev_head + b->ev_pending) % acme_batch::NEV;
-        HIPCHK(be::event_record(b->ev0[slot], st));
+        if ((rc_ = ev_take(b, st, &slot)) != ACME_OK) return rc_;
         if (b->coop_gpw > 0) {
             fill_coop(b, A);
             HIPCHK(be::launch_coop(A, coop_lds_bytes(b->G.H, b->coop_imgl != 0, b->coop_wpb, b->coop_gpw, b->coop_nc), st));
         } else {
             HIPCHK(be::launch_generic(A, st));
         }
-        HIPCHK(be::event_record(b->ev1[slot], st));
-        ++b->ev_pending;
-        b->samples_done += T;
-        if (slot_out) *slot_out = slot;
-        return ACME_OK;
+        return ev_commit(b, st, slot, T, slot_out);
     }
     KArgs A{};
     fill_args(b, A);
@@ -1182,37 +1223,23 @@ static int launch_run(acme_batch *b, const double *du, double *dy, long long T, 
     A.u_ready = u_ready;
     const unsigned grid = (unsigned)((b->N + INST_PER_BLOCK - 1) / INST_PER_BLOCK);
     if (b->iso_thr > 0.0 && !use_lane_kernel(b)) {
-        int rc_ = classify_slow(b, st);
+        rc_ = classify_slow(b, st);
         if (rc_ != ACME_OK) return rc_;
     }
     if (!b->map_slow.empty() && !use_lane_kernel(b)) {
         // two launches: the slow instances on their own stream, everything else on the caller's (timed by the events)
-        if (b->ev_pending == acme_batch::NEV) {
-            int rc_ = drain_events(b, 1);
-            if (rc_ != ACME_OK) return rc_;
-        }
-        const int slot = (b->ev_head + b->ev_pending) % acme_batch::NEV;
         KArgs F = A, S_ = A;
         F.inst_map = b->d_map_fast; F.n_inst = (long long)b->map_fast.size();
         S_.inst_map = b->d_map_slow; S_.n_inst = (long long)b->map_slow.size();
         // (the slow group's launch is ordered behind everything the caller has queued on `st` -- the copy that brings
         // its u in, a kernel that still reads the buffer y goes to: its stream waits for this point of the caller's)
-        HIPCHK(be::event_record(b->ev0[slot], st));
+        if ((rc_ = ev_take(b, st, &slot)) != ACME_OK) return rc_;
         HIPCHK(be::stream_wait_event(b->slow_stream, b->ev0[slot]));
         HIPCHK(b->kf->launch(S_, (unsigned)((S_.n_inst + INST_PER_BLOCK - 1) / INST_PER_BLOCK), b->lds_bytes, b->slow_stream));
         if (F.n_inst > 0) HIPCHK(b->kf->launch(F, (unsigned)((F.n_inst + INST_PER_BLOCK - 1) / INST_PER_BLOCK), b->lds_bytes, st));
-        HIPCHK(be::event_record(b->ev1[slot], st));
-        ++b->ev_pending;
-        b->samples_done += T;
-        if (slot_out) *slot_out = slot;
-        return ACME_OK;
+        return ev_commit(b, st, slot, T, slot_out);
     }
-    if (b->ev_pending == acme_batch::NEV) {  // ring full: retire the oldest pair
-        int rc_ = drain_events(b, 1);
-        if (rc_ != ACME_OK) return rc_;
-    }
-    const int slot = (b->ev_head + b->ev_pending) % acme_batch::NEV;
-    HIPCHK(be::event_record(b->ev0[slot], st));
+    if ((rc_ = ev_take(b, st, &slot)) != ACME_OK) return rc_;
     if (use_lane_kernel(b)) {
         // instances per wave: as few as still give every SIMD of the chip (1 024) no more than one wave -- the
         // batch's run time is one wave's, and a wave's Newton loop lasts as long as its slowest lane's
@@ -1226,7 +1253,7 @@ static int launch_run(acme_batch *b, const double *du, double *dy, long long T, 
     }
     else {
         long long slots = 0;
-        int rc_ = place_waves(b, st, &slots);
+        rc_ = place_waves(b, st, &slots);
         if (rc_ != ACME_OK) return rc_;
         // (a streamed host-buffer run: the kernel variant that waits for its u tiles to land, KArgs::u_ready)
         const auto launch = u_ready ? b->kf->launch_stream : b->kf->launch;
@@ -1238,11 +1265,7 @@ static int launch_run(acme_batch *b, const double *du, double *dy, long long T, 
         } else
             HIPCHK(launch(A, grid, b->lds_bytes, st));
     }
-    HIPCHK(be::event_record(b->ev1[slot], st));
-    ++b->ev_pending;
-    b->samples_done += T;
-    if (slot_out) *slot_out = slot;
-    return ACME_OK;
+    return ev_commit(b, st, slot, T, slot_out);
 }
 
 // soft: a staging buffer that cannot be had is no error (the caller takes another path) and leaves none behind
@@ -1273,13 +1296,120 @@ static bool streamed_fits(const acme_batch *b) {
     return blocks <= per_cu * cus;
 }
 
+}  // extern "C" (the pipeline's driver is a template)
+
+// ---- host-buffer runs in time slices ------------------------------------------------------------------------------------------
+// Long runs on host arrays go through HBM in time slices, two staging buffers each way: while slice s computes (state
+// carries over from launch to launch, bit-identically), copy_stream brings in the input rows of slice s + 1 and
+// copy_stream_out takes out the output rows of slice s - 1.  Slices is such a run's geometry, run_slices its ordering.
+struct Slices {
+    long long T, TS;                // samples of the run, of a slice (the last one may be shorter)
+    size_t N;
+    int nin, nout;                  // rows per sample that come in / go out
+    const double *u;                // the caller's [N][T][nin] ...
+    double *y;                      // ... and [N][T][nout]; NULL: the outputs are not kept
+    double *d_in, *d_out;           // staging, two slices each: slice s uses half s & 1
+    be::stream_t cs, cso;
+    long long ns() const { return (T + TS - 1) / TS; }
+    long long len(long long s) const { return (s + 1) * TS <= T ? TS : T - s * TS; }
+    double *in(long long s) const { return d_in + (s & 1) * (N * (size_t)TS * nin); }
+    double *out(long long s) const { return y ? d_out + (s & 1) * (N * (size_t)TS * nout) : nullptr; }
+    int copy_in(long long s) const {            // (packed: an instance's rows len(s) apart)
+        if (!nin) return 0;
+        const size_t w = sizeof(double) * (size_t)len(s) * nin;
+        return be::copy2d_h2d_async(in(s), w, u + (size_t)s * TS * nin, sizeof(double) * (size_t)T * nin, w, N, cs);
+    }
+    int copy_out(long long s) const {
+        if (!nout || !y) return 0;
+        const size_t w = sizeof(double) * (size_t)len(s) * nout;
+        return be::copy2d_d2h_async(y + (size_t)s * TS * nout, sizeof(double) * (size_t)T * nout, out(s), w, w, N, cso);
+    }
+};
+static int copy_streams(acme_batch *b, bool out) {
+    if (!b->copy_stream) HIPCHK(be::stream_create_nonblocking(&b->copy_stream));
+    if (out && !b->copy_stream_out) HIPCHK(be::stream_create_nonblocking(&b->copy_stream_out));
+    return ACME_OK;
+}
+// The slice length of the fully staged pipeline: only the first copy-in and the last copy-out are exposed, so many small
+// slices -- 24 for a second of audio: a launch costs microseconds, a slice of the headline workload 0.5 GB of copies
+static long long staged_slice(long long T) {
+    if (T < 4096) return T;
+    long long want = 24;
+    if (const char *es = getenv("ACME_HOST_STAGED_SLICES")) { const long long v = atoll(es); if (v >= 1 && v <= 4096) want = v; }
+    const long long TS = ((T / want + CHUNK - 1) / CHUNK) * CHUNK;
+    if (TS < 1024 && want <= 24) return 1024;
+    return TS < CHUNK ? CHUNK : TS;
+}
+// How a slice's outputs leave, the default: the calling thread issues the copy on copy_stream_out -- behind the copy-in of
+// the same step: from pageable memory the call of a copy-out returns when the copy is done, that of a copy-in earlier
+struct CopyOut {
+    const Slices &g;
+    int ready(long long) { return 0; }          // (wait() has seen every earlier copy out)
+    int hand_over(long long) { return 0; }
+    int issue(long long s) { return g.copy_out(s); }
+    int wait() { return be::stream_sync(g.cso); }
+    int last(long long s) { const int rc = g.copy_out(s); return rc != 0 ? rc : be::stream_sync(g.cso); }
+};
+// ... and through a helper thread per slice, for copies that block the thread that issues them
+struct ThreadCopyOut {
+    const Slices &g;
+    const int dev;
+    std::future<int> done[2] = {};
+    int blocking(long long s) const {
+        DeviceGuard d(dev);
+        if (d.rc != 0) return d.rc;
+        const int rc = g.copy_out(s);
+        return rc != 0 ? rc : be::stream_sync(g.cso);
+    }
+    int ready(long long s) { return done[s & 1].valid() ? done[s & 1].get() : 0; }     // the y rows of slice s-2 have left
+    int hand_over(long long s) { done[s & 1] = std::async(std::launch::async, [this, s] { return blocking(s); }); return 0; }
+    int issue(long long) { return 0; }
+    int wait() { return 0; }                    // (the slices overlap; ready() waits when the buffer is needed)
+    int last(long long s) {
+        for (long long k = 0; k < 2; ++k) if (const int rc = ready(k)) return rc;
+        return blocking(s);
+    }
+    ~ThreadCopyOut() { for (auto &f : done) if (f.valid()) (void)f.get(); }             // (an error return: no thread is left behind)
+};
+// The pipeline.  enqueue(s, in, out, n, &done) puts slice s -- n samples, inputs in `in`, outputs to `out` -- on the launch
+// stream and names the event that marks it done; `out` is how the outputs leave (CopyOut, ThreadCopyOut).  Slice s is
+// enqueued before slice s-1 is waited for, so the device never idles between them; the copies of s+1 and s-1 run beside it.
+template <class Enqueue, class Out>
+static int run_slices(acme_batch *b, const Slices &g, Enqueue enqueue, Out &&out) {
+    const long long ns = g.ns();
+    be::event_t prev{}, done{};
+    HIPCHK(g.copy_in(0));
+    HIPCHK(be::stream_sync(g.cs));
+    for (long long s = 0; s < ns; ++s, prev = done) {
+        HIPCHK(out.ready(s));                                           // out(s) may be written
+        const int rc = enqueue(s, g.in(s), g.out(s), g.len(s), &done);
+        if (rc != ACME_OK) return rc;
+        if (s > 0) HIPCHK(be::event_sync(prev));                        // slice s-1 done: its buffers are free
+        if (s > 0 && b->slow_stream) HIPCHK(be::stream_sync(b->slow_stream));   // (... the isolated slow group's, too)
+        // (hand_over and issue are two hooks on purpose: a hand-over to a helper thread must come BEFORE the copy-in, whose
+        // call may block, a copy-out on the stream stays BEHIND it -- merging them changes one caller's order)
+        if (s > 0) HIPCHK(out.hand_over(s - 1));
+        if (s + 1 < ns) HIPCHK(g.copy_in(s + 1));                       // both overlap slice s, and each other
+        if (s > 0) HIPCHK(out.issue(s - 1));
+        if (s + 1 < ns) HIPCHK(be::stream_sync(g.cs));
+        if (s > 0) HIPCHK(out.wait());
+        if (s > 0 && b->progress) b->progress(b->progress_user, s * g.TS, g.T);
+    }
+    HIPCHK(be::event_sync(prev));
+    if (b->slow_stream) HIPCHK(be::stream_sync(b->slow_stream));
+    HIPCHK(out.last(ns - 1));
+    if (b->progress) b->progress(b->progress_user, g.T, g.T);
+    return ACME_OK;
+}
+
+extern "C" {
+
 // ---- oversampled runs (acme_batch_set_oversampling) and measured runs (acme_batch_set_measurement) ----------------------
 // Time slice by time slice on the launch stream: [put the full input rows together (run_const)] -> interpolate to the model
 // rate (acme_resample.h) -> the UNCHANGED run kernel over k x the slice's samples -> decimate -> [measure the slice's
 // base-rate outputs (acme_measure.h)]; the histories carry the signals' past from slice to slice and call to call.  The
 // model-rate scratch is one slice's (ACME_OS_SLICE base-rate samples, default 4 096: config 5 -- 2 048 instances at k = 4 --
-// 0.8 GB).  Host buffers: the staged pipeline of run_impl, two staging buffers each way, the copies of slices s + 1 (in) and
-// s - 1 (out) beside slice s; never the streamed path.
+// 0.8 GB).  Host buffers: run_slices, as run_impl's staged pipeline; never the streamed path.
 // k = 1 (a measurement without oversampling): there is nothing to resample -- the run kernel reads the slice's input rows and
 // writes its outputs where the measurement reads them.  Device arrays with y stored run as ONE slice, the launch a plain run
 // makes; y = NULL: outputs go to one slice of scratch (meas.d_ys) and are never copied anywhere.
@@ -1287,6 +1417,11 @@ static long long os_slice(long long T) {
     long long TS = 4096;
     if (const char *e = getenv("ACME_OS_SLICE")) { const long long v = atoll(e); if (v >= 1) TS = v; }
     return T < TS ? T : TS;
+}
+// the source kernel keeps TABLE rows in LDS unless ACME_SOURCE_LDS=0 (A/B measurements, tests)
+static bool source_lds() {
+    const char *e = getenv("ACME_SOURCE_LDS");
+    return !(e && e[0] == '0');
 }
 static int os_grow(double **p, size_t *cap, size_t bytes) {
     if (bytes > *cap) {
@@ -1348,12 +1483,11 @@ static int run_os(acme_batch *b, const double *u, const double *u_const, unsigne
     for (int r = 0; r < nu && r < 64; ++r) nin -= ((sourced ? b->src.mask : const_mask) >> r & 1ull) ? 1 : 0;
     const bool host = mem == ACME_MEM_HOST, expand = !sourced && const_mask != 0ull, keep = y != nullptr;
     const long long TS = k == 1 && !host && keep && !sourced ? T : os_slice(T), ns = (T + TS - 1) / TS;
-    auto len = [&](long long s) { return (s + 1) * TS <= T ? TS : T - s * TS; };
     // (k = 1: the slices of caller's device arrays are packed into d_base when they are not whole)
     const bool pack = k == 1 && !host && !expand && !sourced && nu && ns > 1;
     // (sourced, k = 1, y in device memory: the run kernel writes a slice's outputs packed; they go to y from scratch)
     const bool scatter = sourced && k == 1 && !host && keep && ny && ns > 1;
-    const bool use_lds = [] { const char *e = getenv("ACME_SOURCE_LDS"); return !(e && e[0] == '0'); }();     // (A/B measurements, tests)
+    const bool use_lds = source_lds();
     int rc = ACME_OK;
     if (k > 1) rc = os_grow(&O.d_ou, &O.cap_ou, sizeof(double) * N * (size_t)(k * TS) * nu);
     if (rc == ACME_OK && k > 1) rc = os_grow(&O.d_oy, &O.cap_oy, sizeof(double) * N * (size_t)(k * TS) * ny);
@@ -1368,14 +1502,11 @@ static int run_os(acme_batch *b, const double *u, const double *u_const, unsigne
         HIPCHK(be::copy_h2d_async(b->d_uc, u_const, sizeof(double) * N * (size_t)nu, st));
         uc = b->d_uc;
     }
-    auto ubuf = [&](long long s) { return b->d_u + (s & 1) * (N * (size_t)TS * nin); };
-    auto ybuf = [&](long long s) { return b->d_y + (s & 1) * (N * (size_t)TS * ny); };
     const double *g = O.d_taps, *h = O.d_taps + O.lu;
-    // slice s on the launch stream
-    auto slice = [&](long long s) -> int {
-        const long long n = len(s), nk = n * k;
-        const double *src = host ? ubuf(s) : u + (size_t)s * TS * nin;
-        long long pitch = host ? n : T;
+    // slice s of n samples on the launch stream: inputs at src, an instance's rows `pitch` samples apart; host arrays: base-rate
+    // outputs to ydst
+    auto slice = [&](long long s, const double *src, long long pitch, double *ydst, long long n) -> int {
+        const long long nk = n * k;
         if (expand || pack) {
             HIPCHK(be::launch_expand(O.d_base, src, expand ? uc : src, const_mask, (long long)N, n, pitch, nu, nin, st));
             src = O.d_base;
@@ -1390,7 +1521,7 @@ static int run_os(acme_batch *b, const double *u, const double *u_const, unsigne
         }
         if (sourced) b->src.clock += n;
         // the slice's base-rate outputs
-        double *dst = !keep ? M.d_ys : host ? ybuf(s) : scatter ? b->src.d_ys : y + (size_t)s * TS * ny;
+        double *dst = !keep ? M.d_ys : host ? ydst : scatter ? b->src.d_ys : y + (size_t)s * TS * ny;
         const long long ypitch = keep && !host && !scatter ? T : n;
         if (k == 1) {
             const int rc_ = launch_run(b, src, dst, n, st, nullptr);
@@ -1419,7 +1550,7 @@ static int run_os(acme_batch *b, const double *u, const double *u_const, unsigne
     };
     if (!host) {
         for (long long s = 0; s < ns; ++s) {
-            rc = slice(s);
+            rc = slice(s, u + (size_t)s * TS * nin, T, nullptr, (s + 1) * TS <= T ? TS : T - s * TS);
             if (rc != ACME_OK) return rc;
         }
         if (b->progress) b->progress(b->progress_user, T, T);
@@ -1430,44 +1561,19 @@ static int run_os(acme_batch *b, const double *u, const double *u_const, unsigne
         (void)ensure_registered(b->reg_u, u, sizeof(double) * N * (size_t)T * (nin ? nin : 1));
         if (keep) (void)ensure_registered(b->reg_y, y, sizeof(double) * N * (size_t)T * ny);
     }
-    if (!b->copy_stream) HIPCHK(be::stream_create_nonblocking(&b->copy_stream));
-    if (!b->copy_stream_out) HIPCHK(be::stream_create_nonblocking(&b->copy_stream_out));
-    const be::stream_t cs = b->copy_stream, cso = b->copy_stream_out;
-    auto copy_in = [&](long long s) -> int {          // (packed: an instance's rows len(s) apart)
-        if (!nin) return 0;
-        const size_t w = sizeof(double) * (size_t)len(s) * nin;
-        return be::copy2d_h2d_async(ubuf(s), w, u + (size_t)s * TS * nin, sizeof(double) * (size_t)T * nin, w, N, cs);
-    };
-    auto copy_out = [&](long long s) -> int {
-        if (!ny || !keep) return 0;
-        const size_t w = sizeof(double) * (size_t)len(s) * ny;
-        return be::copy2d_d2h_async(y + (size_t)s * TS * ny, sizeof(double) * (size_t)T * ny, ybuf(s), w, w, N, cso);
-    };
-    HIPCHK(copy_in(0));
-    HIPCHK(be::stream_sync(cs));
-    for (long long s = 0; s < ns; ++s) {
-        rc = slice(s);
-        if (rc != ACME_OK) return rc;
-        HIPCHK(be::event_record(O.ev[s & 1], st));
-        if (s > 0) HIPCHK(be::event_sync(O.ev[(s - 1) & 1]));       // slice s-1 done: its buffers are free
-        if (s + 1 < ns) HIPCHK(copy_in(s + 1));                      // both overlap slice s, and each other
-        if (s > 0) HIPCHK(copy_out(s - 1));
-        if (s + 1 < ns) HIPCHK(be::stream_sync(cs));
-        if (s > 0) HIPCHK(be::stream_sync(cso));
-        if (s > 0 && b->progress) b->progress(b->progress_user, s * TS, T);     // (base-rate samples)
-    }
-    HIPCHK(be::event_sync(O.ev[(ns - 1) & 1]));
-    HIPCHK(copy_out(ns - 1));
-    HIPCHK(be::stream_sync(cso));
-    if (b->progress) b->progress(b->progress_user, T, T);
-    return ACME_OK;
+    if ((rc = copy_streams(b, true)) != ACME_OK) return rc;
+    const Slices sl{T, TS, N, nin, ny, u, y, b->d_u, b->d_y, b->copy_stream, b->copy_stream_out};
+    return run_slices(b, sl, [&](long long s, const double *in, double *out, long long n, be::event_t *done) -> int {
+        const int rc_ = slice(s, in, n, out, n);
+        if (rc_ != ACME_OK) return rc_;
+        HIPCHK(be::event_record(*done = O.ev[s & 1], st));       // (slice s has been decimated and measured)
+        return ACME_OK;
+    }, CopyOut{sl});      // (progress in base-rate samples)
 }
 
 static int run_impl(acme_batch *b, const double *u, double *y, long long T, int mem, void *stream);
 int acme_batch_run(acme_batch *b, const double *u, double *y, long long T, int mem, void *stream) {
-    join_worker(b);
-    std::unique_lock<std::mutex> serial;           // (the CPU emulator backend is not re-entrant: a worker of
-    if (std::mutex *m = be::run_mutex()) serial = std::unique_lock<std::mutex>(*m);   // ANOTHER batch may be running)
+    RunGuard serial(b);
     if (b && b->src.armed) return fail(ACME_ERR_INVALID, "acme_batch_run: input rows have sources (acme_batch_set_source_*); use acme_batch_run_sources");
     return run_impl(b, u, y, T, mem, stream);
 }
@@ -1490,9 +1596,7 @@ static int run_impl(acme_batch *b, const double *u, double *y, long long T, int 
     }
     if (mem != ACME_MEM_HOST) return fail(ACME_ERR_INVALID, "mem must be ACME_MEM_HOST or ACME_MEM_DEVICE");
 
-    // Host buffers.  Long runs go through HBM in time slices: while the kernel works on slice s
-    // (state carries over from launch to launch, bit-identically), the copy stream brings in the u
-    // rows of slice s+1 and takes out the y rows of slice s-1.  Two staging buffers each way.
+    // Host buffers.  Long runs go through HBM in time slices (Slices / run_slices above).
     const size_t N = (size_t)b->N;
     // Page-locking (and with it every path that lets the device touch the caller's arrays directly) is for callers who
     // have promised to keep the arrays alive while they stay locked: acme_batch_set_host_retention.  Everyone else gets
@@ -1597,30 +1701,25 @@ static int run_impl(acme_batch *b, const double *u, double *y, long long T, int 
                 if (b->progress) b->progress(b->progress_user, T, T);
                 return ACME_OK;
             }
-            const size_t su = sizeof(double) * N * (size_t)TS * nu;
-            int rc = ensure_staging(b, 2 * su, 0);
+            int rc = ensure_staging(b, 2 * sizeof(double) * N * (size_t)TS * nu, 0);
+            if (rc == ACME_OK) rc = copy_streams(b, false);
             if (rc != ACME_OK) return rc;
-            if (!b->copy_stream) HIPCHK(be::stream_create_nonblocking(&b->copy_stream));
-            const be::stream_t cs = b->copy_stream;
-            auto len = [&](long long s) { return (s + 1) * TS <= T ? TS : T - s * TS; };
-            auto ubuf = [&](long long s) { return b->d_u + (s & 1) * (N * (size_t)TS * nu); };
-            auto copy_in = [&](long long s) -> int {      // (packed: rows len(s) apart)
-                const size_t w = sizeof(double) * (size_t)len(s) * nu;
-                return be::copy2d_h2d_async(ubuf(s), w, u + (size_t)s * TS * nu, sizeof(double) * (size_t)T * nu, w, N, cs);
-            };
+            // (a loop of its own, not run_slices': slice 0 is read in place, the kernel writes y into the caller's array --
+            // nothing is copied out -- and copy-in 1 is issued before the first launch, which waits for no copy)
+            const Slices sl{T, TS, N, nu, 0, u, nullptr, b->d_u, nullptr, b->copy_stream, nullptr};
             int slot_prev = -1, slot = -1;
-            HIPCHK(copy_in(1));
+            HIPCHK(sl.copy_in(1));
             for (long long s = 0; s < ns; ++s) {
-                if (s > 0) HIPCHK(be::stream_sync(cs));                        // slice s of u is in HBM
+                if (s > 0) HIPCHK(be::stream_sync(sl.cs));                     // slice s of u is in HBM
                 double *ys = ny ? (double *)dy + (size_t)s * TS * ny : nullptr;
-                if (s == 0) rc = launch_run(b, (const double *)du, ys, len(0), st, &slot, T, T);
-                else rc = launch_run(b, ubuf(s), ys, len(s), st, &slot, 0, T);
+                if (s == 0) rc = launch_run(b, (const double *)du, ys, sl.len(0), st, &slot, T, T);
+                else rc = launch_run(b, sl.in(s), ys, sl.len(s), st, &slot, 0, T);
                 if (rc != ACME_OK) return rc;
                 if (s > 0) {
                     HIPCHK(be::event_sync(b->ev1[slot_prev]));                 // kernel s-1 done: its u buffer is free, ...
                     if (b->slow_stream) HIPCHK(be::stream_sync(b->slow_stream));
                     if (b->progress) b->progress(b->progress_user, s * TS, T);  // ... its y rows are in the caller's array
-                    if (s + 1 < ns) HIPCHK(copy_in(s + 1));
+                    if (s + 1 < ns) HIPCHK(sl.copy_in(s + 1));
                 }
                 slot_prev = slot;
             }
@@ -1630,16 +1729,7 @@ static int run_impl(acme_batch *b, const double *u, double *y, long long T, int 
             return ACME_OK;
         }
     }
-    // Slices: only the first copy-in and the last copy-out are exposed, so many small slices -- 24 for a second of
-    // audio: a launch costs microseconds, a slice of the headline workload 0.5 GB of copies
-    long long TS = T;
-    if (T >= 4096) {
-        long long want = 24;
-        if (const char *es = getenv("ACME_HOST_STAGED_SLICES")) { const long long v = atoll(es); if (v >= 1 && v <= 4096) want = v; }
-        TS = ((T / want + CHUNK - 1) / CHUNK) * CHUNK;
-        if (TS < 1024 && want <= 24) TS = 1024;
-        if (TS < CHUNK) TS = CHUNK;
-    }
+    const long long TS = staged_slice(T);
     const long long ns = (T + TS - 1) / TS;
     const size_t su = sizeof(double) * N * (size_t)TS * nu, sy = sizeof(double) * N * (size_t)TS * ny;
     int rc = ensure_staging(b, (ns > 1 ? 2 : 1) * su, (ns > 1 ? 2 : 1) * sy);
@@ -1654,53 +1744,22 @@ static int run_impl(acme_batch *b, const double *u, double *y, long long T, int 
         if (b->progress) b->progress(b->progress_user, T, T);
         return ACME_OK;
     }
-    if (!b->copy_stream) HIPCHK(be::stream_create_nonblocking(&b->copy_stream));
-    if (!b->copy_stream_out) HIPCHK(be::stream_create_nonblocking(&b->copy_stream_out));
-    const be::stream_t cs = b->copy_stream, cso = b->copy_stream_out;
-    auto len = [&](long long s) { return (s + 1) * TS <= T ? TS : T - s * TS; };
-    auto ubuf = [&](long long s) { return b->d_u + (s & 1) * (N * (size_t)TS * nu); };
-    auto ybuf = [&](long long s) { return b->d_y + (s & 1) * (N * (size_t)TS * ny); };
-    auto copy_in = [&](long long s) -> int {
-        if (!nu) return 0;
-        const size_t w = sizeof(double) * (size_t)len(s) * nu;
-        return be::copy2d_h2d_async(ubuf(s), w, u + (size_t)s * TS * nu, sizeof(double) * (size_t)T * nu, w, N, cs);
-    };
-    auto copy_out = [&](long long s) -> int {
-        if (!ny) return 0;
-        const size_t w = sizeof(double) * (size_t)len(s) * ny;
-        return be::copy2d_d2h_async(y + (size_t)s * TS * ny, sizeof(double) * (size_t)T * ny, ybuf(s), w, w, N, cso);
-    };
-    int slot_prev = -1, slot = -1;
-    HIPCHK(copy_in(0));
-    HIPCHK(be::stream_sync(cs));
-    for (long long s = 0; s < ns; ++s) {
-        rc = launch_run(b, ubuf(s), ybuf(s), len(s), st, &slot);
-        if (rc != ACME_OK) return rc;
-        if (s > 0) HIPCHK(be::event_sync(b->ev1[slot_prev]));       // kernel s-1 done: its buffers are free
-        if (s > 0 && b->slow_stream) HIPCHK(be::stream_sync(b->slow_stream));   // (... the isolated slow group's, too)
-        if (s + 1 < ns) HIPCHK(copy_in(s + 1));                      // both overlap kernel s, and each other
-        if (s > 0) HIPCHK(copy_out(s - 1));
-        if (s + 1 < ns) HIPCHK(be::stream_sync(cs));
-        if (s > 0) HIPCHK(be::stream_sync(cso));
-        if (s > 0 && b->progress) b->progress(b->progress_user, s * TS, T);     // (slice s-1 is in the caller's y)
-        slot_prev = slot;
-    }
-    HIPCHK(be::event_sync(b->ev1[slot_prev]));
-    if (b->slow_stream) HIPCHK(be::stream_sync(b->slow_stream));
-    HIPCHK(copy_out(ns - 1));
-    HIPCHK(be::stream_sync(cso));
-    if (b->progress) b->progress(b->progress_user, T, T);
-    return ACME_OK;
+    if ((rc = copy_streams(b, true)) != ACME_OK) return rc;
+    const Slices sl{T, TS, N, nu, ny, u, y, b->d_u, b->d_y, b->copy_stream, b->copy_stream_out};
+    return run_slices(b, sl, [&](long long, const double *in, double *out, long long n, be::event_t *done) -> int {
+        int slot = 0;
+        const int rc_ = launch_run(b, in, out, n, st, &slot);
+        *done = b->ev1[slot];
+        return rc_;
+    }, CopyOut{sl});      // (a progress report: the slices before are in the caller's y)
 }
 
 // run! with constant input rows (include/acme_hip.h): the varying rows come in (from the host: time slice by time slice, two
-// staging buffers, copies overlapping the kernels as in run_impl's staged pipeline), the full rows of a slice are put
+// staging buffers, copies overlapping the kernels: run_slices), the full rows of a slice are put
 // together in HBM by a small kernel on the launch stream (be::launch_expand), and the run kernels see what they always see.
 int acme_batch_run_const(acme_batch *b, const double *u_var, const double *u_const, unsigned long long const_mask,
                          double *y, long long T, int mem, void *stream) {
-    join_worker(b);
-    std::unique_lock<std::mutex> serial;
-    if (std::mutex *m = be::run_mutex()) serial = std::unique_lock<std::mutex>(*m);
+    RunGuard serial(b);
     if (!b || T < 0) return fail(ACME_ERR_INVALID, "invalid argument to acme_batch_run_const");
     if (b && b->src.armed) return fail(ACME_ERR_INVALID, "acme_batch_run_const: input rows have sources (acme_batch_set_source_*); use acme_batch_run_sources");
     const int nu = b->P.actual.nu, ny = b->P.actual.ny;
@@ -1717,14 +1776,6 @@ int acme_batch_run_const(acme_batch *b, const double *u_var, const double *u_con
     be::stream_t st = (be::stream_t)stream;
     if (b->os.k > 1 || b->meas.on) return run_os(b, u_var, u_const, const_mask, y, T, mem, st);
     const size_t N = (size_t)b->N;
-    auto grow = [&](double **p, size_t *cap, size_t bytes) -> int {
-        if (bytes > *cap) {
-            (void)be::dfree(*p); *p = nullptr; *cap = 0;
-            HIPCHK(be::dmalloc((void **)p, bytes));
-            *cap = bytes;
-        }
-        return ACME_OK;
-    };
     int rc;
     if (mem == ACME_MEM_DEVICE) {
         rc = ensure_staging(b, sizeof(double) * N * (size_t)T * nu, 0);
@@ -1741,80 +1792,32 @@ int acme_batch_run_const(acme_batch *b, const double *u_var, const double *u_con
         (void)ensure_registered(b->reg_u, u_var, sizeof(double) * N * (size_t)T * (nuv ? nuv : 1));
         (void)ensure_registered(b->reg_y, y, sizeof(double) * N * (size_t)T * ny);
     }
-    rc = grow(&b->d_uc, &b->cap_uc, sizeof(double) * N * (size_t)nu);
+    rc = os_grow(&b->d_uc, &b->cap_uc, sizeof(double) * N * (size_t)nu);
     if (rc != ACME_OK) return rc;
     HIPCHK(be::copy_h2d_async(b->d_uc, u_const, sizeof(double) * N * (size_t)nu, st));
-    long long TS = T;
-    if (T >= 4096) {
-        long long want = 24;
-        if (const char *es = getenv("ACME_HOST_STAGED_SLICES")) { const long long v = atoll(es); if (v >= 1 && v <= 4096) want = v; }
-        TS = ((T / want + CHUNK - 1) / CHUNK) * CHUNK;
-        if (TS < 1024 && want <= 24) TS = 1024;
-        if (TS < CHUNK) TS = CHUNK;
-    }
+    const long long TS = staged_slice(T);
     const long long ns = (T + TS - 1) / TS;
     const int nb = ns > 1 ? 2 : 1;
     const size_t su = sizeof(double) * N * (size_t)TS * nu, sv = sizeof(double) * N * (size_t)TS * (nuv ? nuv : 1), sy = sizeof(double) * N * (size_t)TS * ny;
     rc = ensure_staging(b, nb * su, nb * sy);
+    if (rc == ACME_OK) rc = os_grow(&b->d_uv, &b->cap_uv, nb * sv);
+    if (rc == ACME_OK) rc = copy_streams(b, true);
     if (rc != ACME_OK) return rc;
-    rc = grow(&b->d_uv, &b->cap_uv, nb * sv);
-    if (rc != ACME_OK) return rc;
-    if (!b->copy_stream) HIPCHK(be::stream_create_nonblocking(&b->copy_stream));
-    if (!b->copy_stream_out) HIPCHK(be::stream_create_nonblocking(&b->copy_stream_out));
-    const be::stream_t cs = b->copy_stream, cso = b->copy_stream_out;
-    auto len = [&](long long s) { return (s + 1) * TS <= T ? TS : T - s * TS; };
-    auto ubuf = [&](long long s) { return b->d_u + (s & 1) * (N * (size_t)TS * nu); };
-    auto vbuf = [&](long long s) { return b->d_uv + (s & 1) * (N * (size_t)TS * (nuv ? nuv : 1)); };
-    auto ybuf = [&](long long s) { return b->d_y + (s & 1) * (N * (size_t)TS * ny); };
-    auto copy_in = [&](long long s) -> int {          // (packed: an instance's rows len(s) apart)
-        if (!nuv) return 0;
-        const size_t w = sizeof(double) * (size_t)len(s) * nuv;
-        return be::copy2d_h2d_async(vbuf(s), w, u_var + (size_t)s * TS * nuv, sizeof(double) * (size_t)T * nuv, w, N, cs);
-    };
-    auto copy_out = [&](long long s) -> int {
-        if (!ny) return 0;
-        const size_t w = sizeof(double) * (size_t)len(s) * ny;
-        return be::copy2d_d2h_async(y + (size_t)s * TS * ny, sizeof(double) * (size_t)T * ny, ybuf(s), w, w, N, cso);
-    };
+    const Slices sl{T, TS, N, nuv, ny, u_var, y, b->d_uv, b->d_y, b->copy_stream, b->copy_stream_out};
     // The copies run from pageable memory (nothing of the caller's arrays is kept): such a copy blocks the thread that issues
     // it, so issued from one thread the two directions take turns -- 2.9 GB each way on the headline, ~290 ms of copies for
     // 273 ms of kernels.  The y rows therefore leave through a helper thread of their own: in and out overlap each other
     // and the kernels, and the call is bound by the kernels again.
-    const int dev = b->device;
-    auto copy_out_blocking = [&, dev](long long s) -> int {
-        DeviceGuard g(dev);
-        if (g.rc != 0) return g.rc;
-        const int rc_ = copy_out(s);
-        return rc_ != 0 ? rc_ : be::stream_sync(cso);
-    };
-    std::future<int> out_done[2];
-    auto settle = [&](int k) -> int { return out_done[k].valid() ? out_done[k].get() : 0; };
-    struct Drain { std::future<int> (&f)[2]; ~Drain() { for (auto &x : f) if (x.valid()) (void)x.get(); } } drain{out_done};
-    int slot_prev = -1, slot = -1;
-    HIPCHK(copy_in(0));
-    HIPCHK(be::stream_sync(cs));
-    for (long long s = 0; s < ns; ++s) {
-        HIPCHK(settle((int)(s & 1)));                                 // the y rows of slice s-2 have left: kernel s may write its buffer
+    return run_slices(b, sl, [&](long long s, const double *in, double *out, long long n, be::event_t *done) -> int {
         // (the launch stream is in order: slice s is put together behind kernel s-1 and ahead of kernel s; its buffer is the
-        // one kernel s-2 read)
-        HIPCHK(be::launch_expand(ubuf(s), vbuf(s), b->d_uc, const_mask, (long long)N, len(s), len(s), nu, nuv, st));
-        rc = launch_run(b, ubuf(s), ybuf(s), len(s), st, &slot);
-        if (rc != ACME_OK) return rc;
-        if (s > 0) HIPCHK(be::event_sync(b->ev1[slot_prev]));       // kernel s-1 done: its buffers (and expand s's source) are free
-        if (s > 0 && b->slow_stream) HIPCHK(be::stream_sync(b->slow_stream));
-        if (s > 0) out_done[(s - 1) & 1] = std::async(std::launch::async, copy_out_blocking, s - 1);
-        if (s + 1 < ns) HIPCHK(copy_in(s + 1));
-        if (s + 1 < ns) HIPCHK(be::stream_sync(cs));
-        if (s > 0 && b->progress) b->progress(b->progress_user, s * TS, T);
-        slot_prev = slot;
-    }
-    HIPCHK(be::event_sync(b->ev1[slot_prev]));
-    if (b->slow_stream) HIPCHK(be::stream_sync(b->slow_stream));
-    HIPCHK(settle(0));
-    HIPCHK(settle(1));
-    HIPCHK(copy_out_blocking(ns - 1));
-    if (b->progress) b->progress(b->progress_user, T, T);
-    return ACME_OK;
+        // one kernel s-2 read.  Kernel s done also says that expand s has read its source, `in`)
+        double *full = b->d_u + (s & 1) * (N * (size_t)TS * nu);
+        HIPCHK(be::launch_expand(full, in, b->d_uc, const_mask, (long long)N, n, n, nu, nuv, st));
+        int slot = 0;
+        const int rc_ = launch_run(b, full, out, n, st, &slot);
+        *done = b->ev1[slot];
+        return rc_;
+    }, ThreadCopyOut{sl, b->device});
 }
 
 // run! of one batch without blocking the caller: the same call on a worker thread of the library (a
@@ -1824,24 +1827,7 @@ int acme_batch_run_async(acme_batch *b, const double *u, double *y, long long T,
     if (!b) return fail(ACME_ERR_INVALID, "null batch");
     join_worker(b);
     if (b && b->src.armed) return fail(ACME_ERR_INVALID, "acme_batch_run_async: input rows have sources (acme_batch_set_source_*); use acme_batch_run_sources");
-    if (b->worker_rc != ACME_OK) {       // a failed asynchronous run nobody waited for: reported now, not dropped
-        const int rc = b->worker_rc;
-        b->worker_rc = ACME_OK;
-        return fail(rc, "previous asynchronous run failed: " + b->worker_err);
-    }
-    b->worker_err.clear();
-    try {
-        b->worker = std::thread([=]() {
-            std::unique_lock<std::mutex> serial;           // (the CPU emulator backend is not re-entrant)
-            if (std::mutex *m = be::run_mutex()) serial = std::unique_lock<std::mutex>(*m);
-            // (acme_batch_run joins b->worker first: not from the worker itself)
-            b->worker_rc = run_impl(b, u, y, T, mem, stream);
-            if (b->worker_rc != ACME_OK) b->worker_err = g_err;      // the worker's thread-local message
-        });
-    } catch (const std::exception &e) {
-        return fail(ACME_ERR_HIP, std::string("cannot start the worker thread: ") + e.what());
-    }
-    return ACME_OK;
+    return start_worker(b, [=]() { return run_impl(b, u, y, T, mem, stream); });
 }
 
 // ---- input rows generated on the device (acme_batch_set_source_*, acme_source.h) --------------------------------------------
@@ -2002,40 +1988,20 @@ static int run_sources_impl(acme_batch *b, const double *u_var, double *y, long 
 }
 
 int acme_batch_run_sources(acme_batch *b, const double *u_var, double *y, long long T, int mem, void *stream) {
-    join_worker(b);
-    std::unique_lock<std::mutex> serial;
-    if (std::mutex *m = be::run_mutex()) serial = std::unique_lock<std::mutex>(*m);
+    RunGuard serial(b);
     return run_sources_impl(b, u_var, y, T, mem, stream);
 }
 
 int acme_batch_run_sources_async(acme_batch *b, const double *u_var, double *y, long long T, int mem, void *stream) {
     if (!b) return fail(ACME_ERR_INVALID, "null batch");
     join_worker(b);
-    if (b->worker_rc != ACME_OK) {       // (as acme_batch_run_async)
-        const int rc = b->worker_rc;
-        b->worker_rc = ACME_OK;
-        return fail(rc, "previous asynchronous run failed: " + b->worker_err);
-    }
-    b->worker_err.clear();
-    try {
-        b->worker = std::thread([=]() {
-            std::unique_lock<std::mutex> serial;
-            if (std::mutex *m = be::run_mutex()) serial = std::unique_lock<std::mutex>(*m);
-            b->worker_rc = run_sources_impl(b, u_var, y, T, mem, stream);
-            if (b->worker_rc != ACME_OK) b->worker_err = g_err;
-        });
-    } catch (const std::exception &e) {
-        return fail(ACME_ERR_HIP, std::string("cannot start the worker thread: ") + e.what());
-    }
-    return ACME_OK;
+    return start_worker(b, [=]() { return run_sources_impl(b, u_var, y, T, mem, stream); });
 }
 
 // the input a source run of T samples would feed from the current clock, slice by slice: the source kernel writes into the
 // caller's device array, or into one slice of scratch that is copied out (host arrays; the caller's rows staged likewise)
 int acme_batch_render_sources(acme_batch *b, const double *u_var, double *u_out, long long T, int mem, void *stream) {
-    join_worker(b);
-    std::unique_lock<std::mutex> serial;
-    if (std::mutex *m = be::run_mutex()) serial = std::unique_lock<std::mutex>(*m);
+    RunGuard serial(b);
     if (!b || T < 0 || (T > 0 && !u_out)) return fail(ACME_ERR_INVALID, "invalid argument to acme_batch_render_sources");
     acme_batch::Sources &S = b->src;
     if (!S.armed) return fail(ACME_ERR_INVALID, "acme_batch_render_sources: no input row has a source");
@@ -2048,7 +2014,7 @@ int acme_batch_render_sources(acme_batch *b, const double *u_var, double *u_out,
     const size_t N = (size_t)b->N;
     const bool host = mem == ACME_MEM_HOST, var = nin > 0 && u_var;
     const long long TS = os_slice(T);
-    const bool use_lds = [] { const char *e = getenv("ACME_SOURCE_LDS"); return !(e && e[0] == '0'); }();
+    const bool use_lds = source_lds();
     if (host) {
         HIPCHK(be::device_sync());          // (a run still in flight on another stream may use the scratch)
         int rc = os_grow(&b->os.d_base, &b->os.cap_base, sizeof(double) * N * (size_t)TS * nu);

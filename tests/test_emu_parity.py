@@ -657,13 +657,18 @@ def test_emulated_progress_callback_and_host_buffer_release(emu_lib):
     r.release_host_buffers()                   # idempotent
 
 
+# progress of a staged host run of 4 500 samples: 24 slices wanted, 1 024 samples at least; ACME_HOST_STAGED_SLICES=300: 282 of 16
+STAGED_PROGRESS = [1024, 2048, 3072, 4096, 4500]
+STAGED_PROGRESS_16 = list(range(16, 4500, 16)) + [4500]
+
+
 def test_emulated_host_buffer_pipelines_agree(emu_lib, monkeypatch):
     """run! through host buffers with the 16-lane kernel: the default, streamed pipeline (one launch, u copied into HBM
     chunk by chunk -- KArgs::u_ready; the emulator launches synchronously, so here the copy comes first -- y written in
     place), the sliced one (ACME_HOST_SLICES: y in place, the first time slice of u read in place, the following ones
     staged under the kernel of the slice before; KArgs::u_stride / y_stride), the whole run in place
-    (ACME_HOST_SLICES=1) and the fully staged pipeline (ACME_HOST_ZEROCOPY=0) give the same bits, the sliced ones
-    report progress slice by slice, and the result is the oracle's."""
+    (ACME_HOST_SLICES=1) and the fully staged pipeline (ACME_HOST_ZEROCOPY=0; with ACME_HOST_STAGED_SLICES=300 in 282 slices
+    of 16 samples) give the same bits, the sliced ones report progress slice by slice, and the result is the oracle's."""
     monkeypatch.setenv("ACME_LANE_KERNEL", "0")
     monkeypatch.setenv("ACME_HOST_REGISTER_MIN", "1024")        # (the library page-locks arrays of 1 MB and more)
     m = load("diodeclipper")
@@ -673,7 +678,8 @@ def test_emulated_host_buffer_pipelines_agree(emu_lib, monkeypatch):
     out = {}
     for name, env in (("default", {}), ("8 slices", {"ACME_HOST_SLICES": "8"}), ("in place", {"ACME_HOST_SLICES": "1"}),
                       ("staged", {"ACME_HOST_ZEROCOPY": "0"}), ("3 slices", {"ACME_HOST_SLICES": "3"}),
-                      ("not streamed", {"ACME_HOST_STREAM": "0"})):
+                      ("not streamed", {"ACME_HOST_STREAM": "0"}),
+                      ("staged, 16-sample slices", {"ACME_HOST_ZEROCOPY": "0", "ACME_HOST_STAGED_SLICES": "300"})):
         for k, v in env.items():
             monkeypatch.setenv(k, v)
         seen = []
@@ -681,16 +687,19 @@ def test_emulated_host_buffer_pipelines_agree(emu_lib, monkeypatch):
         r = ModelRunner(m, N, lib=emu_lib, showprogress=False if name == "default" else lambda done, total: seen.append((done, total)))
         r.set_host_retention(True)                 # (these pipelines work on page-locked, mapped arrays: the runner holds them)
         y1 = r.run(u)
+        first = [d for d, _ in seen]               # (the first call's reports)
         y2 = r.run(u[:, :, :4200])                 # (a second call on a sub-range of the same arrays' shape)
-        out[name] = (y1, y2, [d for d, _ in seen])
+        out[name] = (y1, y2, first)
         for k in env:
             monkeypatch.delenv(k)
-    for name in ("8 slices", "in place", "staged", "3 slices", "not streamed"):
+    for name in ("8 slices", "in place", "staged", "3 slices", "not streamed", "staged, 16-sample slices"):
         assert np.array_equal(out[name][0], out["default"][0]) and np.array_equal(out[name][1], out["default"][1]), name
     assert out["8 slices"][2][:5] == [1024, 2048, 3072, 4096, 4500]         # 8 wanted, 1 024 samples at least: 5 slices
     assert out["not streamed"][2][:5] == [1024, 2048, 3072, 4096, 4500]
     assert out["in place"][2][:1] == [4500]
     assert out["3 slices"][2][:3] == [1504, 3008, 4500]
+    assert out["staged"][2] == STAGED_PROGRESS
+    assert out["staged, 16-sample slices"][2] == STAGED_PROGRESS_16
     yref, _ = oracle_run(m, u)
     assert_close(out["default"][0], yref, rtol=1e-12)
     # the default: nothing of the caller's arrays is kept (acme_batch_set_host_retention off) -- the staged pipeline from
@@ -699,6 +708,28 @@ def test_emulated_host_buffer_pipelines_agree(emu_lib, monkeypatch):
     y1 = r.run(u)
     assert np.array_equal(y1, out["default"][0])
     assert getattr(r, "_held", None) is None
+
+
+def test_emulated_run_const_from_host_arrays_in_slices(emu_lib, monkeypatch):
+    """acme_batch_run_const from host arrays (the y rows leave through a helper thread), two input rows of which row 1 is
+    constant: in the default 1 024-sample slices and in 282 slices of 16 (ACME_HOST_STAGED_SLICES=300) the bits are those
+    of run on the materialised input, and progress is reported slice by slice."""
+    from acme_jl_amd.runner import ModelRunner
+    m = load("birdie_var")
+    N, T = 3, 4500
+    ub = np.ascontiguousarray(sweep_inputs("birdie_var", N, T).transpose(0, 2, 1))      # [N][T][2]
+    ub[:, :, 1] = ub[:, :1, 1]                     # (row 1 constant per instance, whatever the sweep holds)
+    y_ref = ModelRunner(m, N, lib=emu_lib).run(ub, time_major=True)
+    for env, progress in (({}, STAGED_PROGRESS), ({"ACME_HOST_STAGED_SLICES": "300"}, STAGED_PROGRESS_16)):
+        for k, v in env.items():
+            monkeypatch.setenv(k, v)
+        seen = []
+        r = ModelRunner(m, N, lib=emu_lib, showprogress=lambda done, total: seen.append((done, total)))
+        y = r.run_const(ub[:, :, :1], ub[:, 0, :], [1])
+        for k in env:
+            monkeypatch.delenv(k)
+        assert np.array_equal(y, y_ref), env
+        assert seen == [(d, T) for d in progress], env
 
 
 def test_emulated_generic_kernel_never_refuses(emu_lib, monkeypatch):

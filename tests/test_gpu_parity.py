@@ -761,8 +761,10 @@ def test_host_buffer_paths_agree_bit_for_bit(hip_lib, monkeypatch):
     outs = {}
     for mode, env in (("one shot", {}), ("default", {}), ("sliced", {}), ("in place", {"ACME_HOST_SLICES": "1"}), ("3 slices", {"ACME_HOST_SLICES": "3"}),
                       ("streamed, 16-sample chunks", {"ACME_HOST_STREAM_CHUNK": "16"}),
-                      ("staged", {"ACME_HOST_ZEROCOPY": "0"}), ("pageable", {"ACME_HOST_REGISTER": "0"})):
-        for k in ("ACME_HOST_ZEROCOPY", "ACME_HOST_REGISTER", "ACME_HOST_SLICES", "ACME_HOST_STREAM_CHUNK"):
+                      ("staged", {"ACME_HOST_ZEROCOPY": "0"}), ("pageable", {"ACME_HOST_REGISTER": "0"}),
+                      # (282 slices, the last of 5 samples: the ring of 32 event pairs wraps eight times)
+                      ("staged, 16-sample slices", {"ACME_HOST_ZEROCOPY": "0", "ACME_HOST_STAGED_SLICES": "300"})):
+        for k in ("ACME_HOST_ZEROCOPY", "ACME_HOST_REGISTER", "ACME_HOST_SLICES", "ACME_HOST_STREAM_CHUNK", "ACME_HOST_STAGED_SLICES"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -785,7 +787,7 @@ def test_host_buffer_paths_agree_bit_for_bit(hip_lib, monkeypatch):
         assert streamed or (seen and seen[-1] == (T, T))
         outs[mode] = (yb.copy(), r.report_arrays()["iters_total"].copy(), [a.copy() for a in r.get_state()])
         r.release_host_buffers()
-    for k in ("ACME_HOST_ZEROCOPY", "ACME_HOST_REGISTER", "ACME_HOST_SLICES", "ACME_HOST_STREAM_CHUNK"):
+    for k in ("ACME_HOST_ZEROCOPY", "ACME_HOST_REGISTER", "ACME_HOST_SLICES", "ACME_HOST_STREAM_CHUNK", "ACME_HOST_STAGED_SLICES"):
         monkeypatch.delenv(k, raising=False)
     r = ModelRunner(m, N, lib=hip_lib)
     yd = r.run_torch(torch.from_numpy(ub).cuda()).cpu().numpy()
@@ -1066,9 +1068,10 @@ def test_mid_size_kernel(hip_lib, monkeypatch):
             assert np.abs(y - ylit).max() <= RTOL_SAME * scale
 
 
-def test_constant_input_rows(hip_lib):
+def test_constant_input_rows(hip_lib, monkeypatch):
     """acme_batch_run_const on the GPU: the headline model with its three potentiometer rows handed over once per instance
-    -- host arrays (sliced pipeline: 9 000 samples) and device arrays -- gives the bits of run on the materialised input."""
+    -- host arrays (sliced pipeline: 9 000 samples; 4 501 samples in 282 slices of 16, each handing its y rows to the
+    helper thread) and device arrays -- gives the bits of run on the materialised input."""
     import ctypes as C
     import torch
     from acme_jl_amd.model import CachingHomotopySolver
@@ -1087,6 +1090,16 @@ def test_constant_input_rows(hip_lib):
                                                torch.cuda.current_stream().cuda_stream))
     torch.cuda.synchronize()
     assert np.array_equal(yd.cpu().numpy(), y_ref)
+    T2 = 4501
+    uv2, yd2 = uv[:, :T2].contiguous(), torch.empty((N, T2, m.ny), dtype=torch.float64, device="cuda")
+    rd2 = runner(hip_lib, m, N)
+    rd2.lib.check(rd2.lib.L.acme_batch_run_const(rd2.h, uv2.data_ptr(), uc.data_ptr(), 0b1110, yd2.data_ptr(), T2, ACME_MEM_DEVICE,
+                                                 torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    monkeypatch.setenv("ACME_HOST_STAGED_SLICES", "300")
+    y2 = runner(hip_lib, m, N).run_const(ub[:, :T2, :1], ub[:, 0, :], (1, 2, 3))
+    monkeypatch.delenv("ACME_HOST_STAGED_SLICES")
+    assert np.array_equal(y2, yd2.cpu().numpy())
 
 
 def test_streamed_host_path_only_when_the_grid_is_resident(hip_lib):

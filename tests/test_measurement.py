@@ -128,6 +128,30 @@ def test_slices_calls_memory_entry_points_and_y_null_are_bit_identical(emu_lib, 
         assert np.array_equal(out, ref[0]), k
 
 
+def test_measured_host_run_in_many_slices_reports_progress(emu_lib, monkeypatch):
+    """a measured run from host arrays in 63 slices of 16 samples (ACME_OS_SLICE=16, T = 1 000), y stored and y = NULL: progress
+    after every slice, outputs and accumulators those of the run in one slice"""
+    m = load("birdie_var", HS)
+    N, T = 3, 1000
+    u = birdie_u(N, T)
+    spec = dict(start=4, f0=Fraction(1000, FS), harmonics=4)
+    got = {}
+    for sl in ("4096", "16"):
+        monkeypatch.setenv("ACME_OS_SLICE", sl)
+        for keep in (True, False):
+            seen = []
+            r = runner(m, N, emu_lib, showprogress=lambda done, total: seen.append((done, total))).set_measurement(**spec)
+            y = r.run(u, time_major=True) if keep else None
+            if not keep:
+                r.measure(u, time_major=True)
+            got[sl, keep] = (y, raw(r))
+            assert seen == ([(T, T)] if sl == "4096" else [(d, T) for d in list(range(16, T, 16)) + [T]]), (sl, keep)
+    monkeypatch.delenv("ACME_OS_SLICE")
+    assert np.array_equal(got["16", True][0], got["4096", True][0])
+    for key, (_, (out, count)) in got.items():
+        assert count == got["4096", True][1][1] and np.array_equal(out, got["4096", True][1][0]), key
+
+
 # ---- 3. windows ------------------------------------------------------------------------------------------------------------
 def test_windows_straddle_calls_and_slices_and_reset_restarts(emu_lib, monkeypatch):
     m = clipper()
