@@ -167,6 +167,14 @@ struct acme_batch {
         std::vector<long long> fold_per;         // [N]: the instances' periods
         long long *d_fold_per = nullptr;         // [N]
         double *d_fold = nullptr;                // [N nrows][fold_pmax] sums, from 0.0
+        // spectrum (acme_batch_set_measurement_spectrum): Welch-averaged periodograms of the window, segments of spec_L
+        // samples every spec_hop
+        bool spec = false;
+        long long spec_L = 0, spec_hop = 0;
+        std::vector<double> spec_w, spec_tw;     // [L] the window, [L / 2][2] the twiddles, as the device has them
+        double *d_spec_w = nullptr, *d_spec_tw = nullptr;
+        double *d_spec_acc = nullptr;            // [N nrows][L / 2 + 1] sums of |X_k|^2, from 0.0
+        double *d_spec_carry = nullptr;          // [N nrows][L]: the window's most recent samples, sample m at m mod L
     } meas;
     // Input rows generated on the device (acme_batch_set_source_*, acme_source.h): the rows' descriptions and per-instance
     // parameters in device memory, the source clock
@@ -779,6 +787,7 @@ static void meas_release(acme_batch::Measurement &M) {
     (void)be::dfree(M.d_fnum_g); (void)be::dfree(M.d_perm); (void)be::dfree(M.d_sgrp); (void)be::dfree(M.d_wgrp);
     (void)be::dfree(M.d_kbin_g);
     (void)be::dfree(M.d_fold_per); (void)be::dfree(M.d_fold);
+    (void)be::dfree(M.d_spec_w); (void)be::dfree(M.d_spec_tw); (void)be::dfree(M.d_spec_acc); (void)be::dfree(M.d_spec_carry);
     M = acme_batch::Measurement{};
 }
 
@@ -1463,6 +1472,12 @@ static int meas_step(acme_batch *b, const double *y, long long n, long long pitc
             memcpy(G.row, M.row, sizeof(G.row));
             HIPCHK(meas_fold_launch(G, st));
         }
+        if (M.spec) {   // ... and the segments that end in this chunk
+            MeasSpecArgs G{y, M.d_spec_acc, M.d_spec_carry, M.d_spec_w, M.d_spec_tw, b->N, len, pitch, s - M.pos, s - M.start,
+                           M.spec_L, M.spec_hop, A.ny, M.nrows, {}};
+            memcpy(G.row, M.row, sizeof(G.row));
+            HIPCHK(meas_spectrum_launch(G, st));
+        }
     }
     M.pos += n;
     return ACME_OK;
@@ -2124,6 +2139,11 @@ static int meas_zero(acme_batch *b) {
         HIPCHK(meas_fold_zero(M.d_fold, P * (size_t)M.fold_pmax));
         HIPCHK(be::device_sync());
     }
+    if (M.spec) {       // the sums and the carried samples (L, hop, the window and the table stay)
+        HIPCHK(meas_spectrum_zero(M.d_spec_acc, P * (size_t)(M.spec_L / 2 + 1)));
+        HIPCHK(meas_spectrum_zero(M.d_spec_carry, P * (size_t)M.spec_L));
+        HIPCHK(be::device_sync());
+    }
     M.pos = 0;
     return ACME_OK;
 }
@@ -2294,6 +2314,7 @@ int acme_batch_set_measurement_series(acme_batch *b, long long win, long long ho
     acme_batch::Measurement &M = b->meas;
     if (!M.on) return fail(ACME_ERR_INVALID, "measurement series: no measurement is armed");
     if (M.fold) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a fold (a fold per window is not supported)");
+    if (M.spec) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a spectrum (a spectrum per window is not supported)");
     if (M.length != 0) return fail(ACME_ERR_INVALID, "measurement series: the armed measurement's length must be 0 (the series sets the windows)");
     if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement series: samples have been fed since arming (arm or reset the measurement first)");
     if (win < 1) return fail(ACME_ERR_INVALID, "measurement series: win must be >= 1");
@@ -2419,6 +2440,99 @@ int acme_batch_get_measurement_fold(acme_batch *b, double *out, long long *perio
 int acme_batch_get_measurement_fold_sums(acme_batch *b, double *out) {
     if (b && !out) return fail(ACME_ERR_INVALID, "measurement fold sums: out is null");
     return get_measurement_fold(b, out, nullptr, nullptr, true);
+}
+
+// the spectrum's twiddles: (cos, -sin)(2 pi k / L), k < L / 2, each component the extended-precision value rounded once;
+// exactly (1, 0) at k = 0 and (0, -1) at k = L / 4
+static std::vector<double> spectrum_table(long long L) {
+    std::vector<double> tw((size_t)L);
+    const long double two_pi = 2.0L * acosl(-1.0L);
+    for (long long k = 0; k < L / 2; ++k) {
+        const long double th = two_pi * (long double)k / (long double)L;
+        tw[(size_t)(2 * k)] = (double)cosl(th);
+        tw[(size_t)(2 * k + 1)] = (double)-sinl(th);
+    }
+    tw[0] = 1.0; tw[1] = 0.0;
+    tw[(size_t)(L / 2)] = 0.0; tw[(size_t)(L / 2 + 1)] = -1.0;
+    return tw;
+}
+
+int acme_batch_set_measurement_spectrum(acme_batch *b, long long L, long long hop, const double *w) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    acme_batch::Measurement &M = b->meas;
+    if (!M.on) return fail(ACME_ERR_INVALID, "measurement spectrum: no measurement is armed");
+    if (M.W) return fail(ACME_ERR_UNSUPPORTED, "measurement spectrum: the measurement has a series of windows (a spectrum per window is not supported)");
+    if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement spectrum: samples have been fed since arming (arm or reset the measurement first)");
+    if (L < MEAS_MIN_SPECTRUM || L > MEAS_MAX_SPECTRUM || (L & (L - 1)) != 0)
+        return fail(ACME_ERR_INVALID, "measurement spectrum: L must be a power of two, " + std::to_string(MEAS_MIN_SPECTRUM) + " ... " +
+                                          std::to_string(MEAS_MAX_SPECTRUM));
+    if (hop < 1 || hop > L) return fail(ACME_ERR_INVALID, "measurement spectrum: hop is outside 1 ... L");
+    std::vector<double> win((size_t)L, 1.0);
+    for (long long j = 0; w && j < L; ++j) {
+        if (!std::isfinite(w[j])) return fail(ACME_ERR_INVALID, "measurement spectrum: w[" + std::to_string(j) + "] is not finite");
+        win[(size_t)j] = w[j];
+    }
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    (void)be::dfree(M.d_spec_w); (void)be::dfree(M.d_spec_tw); (void)be::dfree(M.d_spec_acc); (void)be::dfree(M.d_spec_carry);
+    M.d_spec_w = M.d_spec_tw = M.d_spec_acc = M.d_spec_carry = nullptr;     // (a spectrum set again replaces the earlier one)
+    M.spec = false;
+    std::vector<double> tw = spectrum_table(L);
+    const size_t pairs = (size_t)b->N * (size_t)M.nrows;
+    HIPCHK(be::dmalloc((void **)&M.d_spec_w, sizeof(double) * (size_t)L));
+    HIPCHK(be::dmalloc((void **)&M.d_spec_tw, sizeof(double) * (size_t)L));
+    HIPCHK(be::dmalloc((void **)&M.d_spec_acc, sizeof(double) * pairs * (size_t)(L / 2 + 1)));
+    HIPCHK(be::dmalloc((void **)&M.d_spec_carry, sizeof(double) * pairs * (size_t)L));
+    HIPCHK(be::copy_h2d(M.d_spec_w, win.data(), sizeof(double) * (size_t)L));
+    HIPCHK(be::copy_h2d(M.d_spec_tw, tw.data(), sizeof(double) * (size_t)L));
+    HIPCHK(meas_spectrum_zero(M.d_spec_acc, pairs * (size_t)(L / 2 + 1)));
+    HIPCHK(meas_spectrum_zero(M.d_spec_carry, pairs * (size_t)L));
+    HIPCHK(be::device_sync());
+    M.spec_w = std::move(win);
+    M.spec_tw = std::move(tw);
+    M.spec_L = L;
+    M.spec_hop = hop;
+    M.spec = true;
+    return ACME_OK;
+}
+
+static int get_measurement_spectrum(acme_batch *b, double *out, long long *segments, long long *count, bool sums) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const acme_batch::Measurement &M = b->meas;
+    if (!M.on || !M.spec) return fail(ACME_ERR_INVALID, "no measurement spectrum is set");
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    const long long end = M.length ? M.start + M.length : LLONG_MAX;
+    const long long cnt = (M.pos < end ? M.pos : end) - M.start, c = cnt > 0 ? cnt : 0;
+    const long long S = c >= M.spec_L ? (c - M.spec_L) / M.spec_hop + 1 : 0;
+    if (count) *count = c;
+    if (segments) *segments = S;
+    if (!out) return ACME_OK;
+    const size_t total = (size_t)b->N * M.nrows * (size_t)(M.spec_L / 2 + 1);
+    if (total) HIPCHK(be::copy_d2h(out, M.d_spec_acc, sizeof(double) * total));     // (the accumulators' layout is the result's)
+    for (size_t k = 0; k < total; ++k) out[k] = S == 0 ? NAN : sums ? out[k] : out[k] / (double)S;
+    return ACME_OK;
+}
+
+int acme_batch_get_measurement_spectrum(acme_batch *b, double *out, long long *segments, long long *count) {
+    return get_measurement_spectrum(b, out, segments, count, false);
+}
+
+int acme_batch_get_measurement_spectrum_sums(acme_batch *b, double *out) {
+    if (b && !out) return fail(ACME_ERR_INVALID, "measurement spectrum sums: out is null");
+    return get_measurement_spectrum(b, out, nullptr, nullptr, true);
+}
+
+int acme_batch_get_measurement_spectrum_table(acme_batch *b, double *w, double *tw) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const acme_batch::Measurement &M = b->meas;
+    if (!M.on || !M.spec) return fail(ACME_ERR_INVALID, "no measurement spectrum is set");
+    if (w) memcpy(w, M.spec_w.data(), sizeof(double) * M.spec_w.size());
+    if (tw) memcpy(tw, M.spec_tw.data(), sizeof(double) * M.spec_tw.size());
+    return ACME_OK;
 }
 
 int acme_batch_clear_measurement(acme_batch *b) { return set_measurement(b, nullptr); }

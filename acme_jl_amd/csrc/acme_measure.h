@@ -63,6 +63,15 @@
 // (independent chains: their loads are in flight together); a period below 64 leaves the lanes at and beyond P idle and
 // takes several of a slot's samples ahead of its chain instead.
 //
+// SPECTRUM (acme_batch_set_measurement_spectrum): Welch-averaged periodograms of the window -- segment s covers the window's
+// samples [s hop, s hop + L), L a power of two 64 ... 4096; x = w y, the radix-2 decimation-in-time transform with every
+// operation rounded on its own (no fused multiply-add: include/acme_hip.h has the contract), acc[p][k] += Xr Xr + Xi Xi for
+// k <= L / 2, ONE chain per bin in segment order from 0.0.  The accumulators are [N nrows][L / 2 + 1]; beside them a carry
+// [N nrows][L], a ring per pair with window sample m at m mod L, holds the L most recent samples, so that a segment is
+// transformed in the chunk that holds its last sample whatever chunks, slices and calls it straddles.  One more kernel per
+// chunk (acme_meas_spectrum_kernel<log2 L>): a block of 256 lanes per pair, the vector in LDS, two stages a pass in
+// registers; the emulator walks meas_spectrum_chain, the contract as a plain loop.
+//
 // The per-element functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with g++).
 #pragma once
@@ -215,6 +224,37 @@ ACME_HD inline void meas_fold_chain(const MeasFoldArgs &A, long long p) {
         if (++s == P) s = 0;
     }
 }
+
+// spectrum: Welch-averaged periodograms of the window.  The chunk's first sample is number m0 >= 0 of the window; segment s
+// covers the window's samples [s hop, s hop + L) and is transformed in the chunk that holds its last sample.  The samples
+// of earlier chunks come from the carry, a ring per pair: sample m sits at carry[m mod L] (the L most recent samples).
+constexpr long long MEAS_MIN_SPECTRUM = 64, MEAS_MAX_SPECTRUM = 4096;
+
+struct MeasSpecArgs {
+    const double *y;            // instance i, sample t, row r at y[(i * pitch + t0 + t) * ny + r]
+    double *acc;                // [n * nrows][L / 2 + 1] sums of |X_k|^2, from 0.0
+    double *carry;              // [n * nrows][L]
+    const double *w;            // [L] the window
+    const double *tw;           // [L / 2] pairs: (cos, -sin)(2 pi k / L)
+    long long n, len, pitch, t0, m0, L, hop;
+    int ny, nrows;
+    unsigned char row[64];      // the measured rows, ascending
+};
+
+// the segments whose last sample lies in the chunk [m0, m0 + len): *lo ... *hi (none: *hi < *lo)
+ACME_HD inline void meas_spec_segments(long long m0, long long len, long long L, long long hop, long long *lo, long long *hi) {
+    *lo = m0 >= L ? (m0 - L + hop) / hop : 0;           // s hop + L - 1 >= m0
+    *hi = m0 + len >= L ? (m0 + len - L) / hop : -1;    // s hop + L - 1 < m0 + len
+}
+
+// Every operation of the spectrum is rounded on its own: no fused multiply-add (the compilers contract by default)
+#if defined(__clang__)
+#define ACME_NO_CONTRACT _Pragma("clang fp contract(off)")
+#define ACME_NO_CONTRACT_FN
+#else
+#define ACME_NO_CONTRACT
+#define ACME_NO_CONTRACT_FN __attribute__((optimize("fp-contract=off"), noinline))
+#endif
 
 // NaN sticks: once an accumulator is NaN it stays so
 ACME_HD inline double meas_min(double m, double v) { return (v < m || v != v) ? v : m; }
@@ -708,7 +748,135 @@ __global__ __launch_bounds__(64 * acme::MEAS_FOLD_WAVES) void acme_meas_fold_ker
     for (; cover - cb > 64; cb += 256) acme_meas_fold_span<4, 2>(yp, f, cb, cover, A.len, ph, P, A.ny, lane);
     if (cb < cover) acme_meas_fold_span<1, 8>(yp, f, cb, cover, A.len, ph, P, A.ny, lane);
 }
+
+// spectrum: a block of 256 lanes per pair.  The transform's vector lives in LDS as two arrays of doubles (re, im), element i
+// at i + i / 32: one double of padding per 32 (a bank row of the 8-byte reads), so that the four elements of a lane at the
+// power-of-two strides of the early passes, and the bit-reversed stores of the load, spread over the banks.  A pass keeps
+// two stages in registers: lane work item j owns the elements i0, i0 + h, i0 + 2h, i0 + 3h (i0 = (j / h) 4h + j mod h) and
+// runs the four radix-2 butterflies of stages q + 1 (half-size h) and q + 2 (half-size 2h) on them; an odd log2 L ends in one
+// pass of plain butterflies at h = L / 2.  The first pass never reads the imaginary array (it holds nothing yet: the zeros
+// are formed in registers).  L < 1024 fills the block with G = 1024 / L segments side by side; the bins' owners then add the
+// G power spectra in segment order.  A lane owns bins k = lane + 256 b and keeps their sums in registers over the chunk.
+// The carry is read by the loads only, every load is followed by a barrier of the block, and the rewrite comes behind the
+// last of them.
+__device__ inline void acme_meas_spec_bf(double &ar, double &ai, double &br, double &bi, double wr, double wi) {
+    ACME_NO_CONTRACT
+    const double p0 = wr * br, p1 = wi * bi, p2 = wr * bi, p3 = wi * br;
+    const double tr = p0 - p1, ti = p2 + p3;
+    br = ar - tr;
+    bi = ai - ti;
+    ar = ar + tr;
+    ai = ai + ti;
+}
+template <int LOG2L>
+__global__ __launch_bounds__(256) void acme_meas_spectrum_kernel(acme::MeasSpecArgs A) {
+    ACME_NO_CONTRACT
+    using namespace acme;
+    constexpr int L = 1 << LOG2L, Q = L / 4, G = Q >= 256 ? 1 : 256 / Q, PITCH = L + L / 32, NB = (L / 2 + 256) / 256;
+    __shared__ double sre[G * PITCH], sim[G * PITCH];
+    const int tid = threadIdx.x;
+    const long long p = blockIdx.x, i = p / A.nrows;
+    const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    double *carry = A.carry + p * L, *acc = A.acc + p * (L / 2 + 1);
+    long long s_lo, s_hi;
+    meas_spec_segments(A.m0, A.len, L, A.hop, &s_lo, &s_hi);
+    double a[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) a[b] = s_lo <= s_hi && tid + 256 * b <= L / 2 ? acc[tid + 256 * b] : 0.0;
+    for (long long s0 = s_lo; s0 <= s_hi; s0 += G) {
+        // x = w y of the round's segments, stored in bit-reversed order
+        for (int e = tid; e < G * L; e += 256) {
+            const int g = e >> LOG2L, j = e & (L - 1);
+            if (s0 + g > s_hi) continue;
+            const long long m = (s0 + g) * A.hop + j;
+            const double v = m >= A.m0 ? yp[(m - A.m0) * A.ny] : carry[m & (L - 1)];
+            const int r = (int)(__brev((unsigned)j) >> (32 - LOG2L));
+            sre[g * PITCH + r + (r >> 5)] = A.w[j] * v;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q + 2 <= LOG2L; q += 2) {
+            const int h = 1 << q;
+            for (int e = tid; e < G * Q; e += 256) {
+                const int g = e >> (LOG2L - 2), j = e & (Q - 1), r = j & (h - 1), i0 = ((j >> q) << (q + 2)) + r;
+                if (s0 + g > s_hi) continue;
+                double *re = sre + g * PITCH, *im = sim + g * PITCH;
+                int at[4];
+                double xr[4], xi[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    at[c] = i0 + c * h + ((i0 + c * h) >> 5);
+                    xr[c] = re[at[c]];
+                    xi[c] = q == 0 ? 0.0 : im[at[c]];
+                }
+                const double *ta = A.tw + 2 * ((long long)r << (LOG2L - 1 - q));
+                const double *tb = A.tw + 2 * ((long long)r << (LOG2L - 2 - q));
+                const double *tc = A.tw + 2 * ((long long)(r + h) << (LOG2L - 2 - q));
+                const double ar = ta[0], ai = ta[1], br = tb[0], bi = tb[1], cr = tc[0], ci = tc[1];
+                acme_meas_spec_bf(xr[0], xi[0], xr[1], xi[1], ar, ai);
+                acme_meas_spec_bf(xr[2], xi[2], xr[3], xi[3], ar, ai);
+                acme_meas_spec_bf(xr[0], xi[0], xr[2], xi[2], br, bi);
+                acme_meas_spec_bf(xr[1], xi[1], xr[3], xi[3], cr, ci);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    re[at[c]] = xr[c];
+                    im[at[c]] = xi[c];
+                }
+            }
+            __syncthreads();
+        }
+        if (LOG2L & 1) {                                // the last stage on its own: h = L / 2, twiddle index i
+            for (int e = tid; e < G * (L / 2); e += 256) {
+                const int g = e >> (LOG2L - 1), j = e & (L / 2 - 1);
+                if (s0 + g > s_hi) continue;
+                double *re = sre + g * PITCH, *im = sim + g * PITCH;
+                const int a0 = j + (j >> 5), a1 = j + L / 2 + ((j + L / 2) >> 5);
+                double xr0 = re[a0], xi0 = im[a0], xr1 = re[a1], xi1 = im[a1];
+                acme_meas_spec_bf(xr0, xi0, xr1, xi1, A.tw[2 * j], A.tw[2 * j + 1]);
+                re[a0] = xr0;
+                im[a0] = xi0;
+                re[a1] = xr1;
+                im[a1] = xi1;
+            }
+            __syncthreads();
+        }
+        // |X_k|^2 of the round's segments into the bins' chains, in segment order
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const int k = tid + 256 * b;
+            if (k > L / 2) continue;
+            for (int g = 0; g < G && s0 + g <= s_hi; ++g) {
+                const double xr = sre[g * PITCH + k + (k >> 5)], xi = sim[g * PITCH + k + (k >> 5)];
+                const double pr = xr * xr, pi = xi * xi;
+                const double pw = pr + pi;
+                a[b] = a[b] + pw;
+            }
+        }
+        __syncthreads();                                // (the next round's load overwrites the vectors)
+    }
+    if (s_lo <= s_hi) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+            if (tid + 256 * b <= L / 2) acc[tid + 256 * b] = a[b];
+    }
+    // the chunk's last min(len, L) samples into the ring (every read of it lies before a barrier above)
+    for (long long t = (A.len > L ? A.len - L : 0) + tid; t < A.len; t += 256) carry[(A.m0 + t) & (L - 1)] = yp[t * A.ny];
+}
 namespace acme {
+template <int LOG2L>
+inline int meas_spectrum_launch_l(const MeasSpecArgs &A, hipStream_t st) {
+    if constexpr (LOG2L > 12) {
+        return (int)hipErrorInvalidValue;
+    } else {
+        if ((1ll << LOG2L) != A.L) return meas_spectrum_launch_l<LOG2L + 1>(A, st);
+        hipLaunchKernelGGL(acme_meas_spectrum_kernel<LOG2L>, dim3((unsigned)(A.n * A.nrows)), dim3(256), 0, st, A);
+        return (int)hipGetLastError();
+    }
+}
+inline int meas_spectrum_launch(const MeasSpecArgs &A, hipStream_t st) {
+    return A.n * A.nrows > 0 ? meas_spectrum_launch_l<6>(A, st) : 0;
+}
+inline int meas_spectrum_zero(double *p, size_t count) { return (int)hipMemset(p, 0, sizeof(double) * count); }
 inline int meas_fold_launch(const MeasFoldArgs &A, hipStream_t st) {
     const long long pairs = A.n * A.nrows;
     hipLaunchKernelGGL(acme_meas_fold_kernel, dim3((unsigned)((pairs + MEAS_FOLD_WAVES - 1) / MEAS_FOLD_WAVES)),
@@ -778,6 +946,53 @@ inline int meas_series_launch(const MeasSeriesTwArgs &T, const MeasSeriesArgs &G
 }  // namespace acme
 #else
 namespace acme {
+// spectrum: the contract's arithmetic literally, pair by pair, segment by segment, stage by stage
+ACME_NO_CONTRACT_FN inline void meas_spectrum_chain(const MeasSpecArgs &A, long long p) {
+    ACME_NO_CONTRACT
+    const long long i = p / A.nrows, L = A.L;
+    const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    double *carry = A.carry + p * L, *acc = A.acc + p * (L / 2 + 1);
+    long long s_lo, s_hi;
+    meas_spec_segments(A.m0, A.len, L, A.hop, &s_lo, &s_hi);
+    int bits = 0;
+    while ((1ll << bits) < L) ++bits;
+    std::vector<double> vr((size_t)L), vi((size_t)L);
+    for (long long s = s_lo; s <= s_hi; ++s) {
+        for (long long j = 0; j < L; ++j) {
+            const long long m = s * A.hop + j;
+            long long r = 0;
+            for (int k = 0; k < bits; ++k) r |= (j >> k & 1) << (bits - 1 - k);
+            vr[(size_t)r] = A.w[j] * (m >= A.m0 ? yp[(m - A.m0) * A.ny] : carry[m & (L - 1)]);
+            vi[(size_t)r] = 0.0;
+        }
+        for (long long h = 1; h < L; h *= 2)
+            for (long long i0 = 0; i0 < L; ++i0) {
+                if (i0 & h) continue;
+                const long long k = (i0 & (h - 1)) * (L / (2 * h));
+                const double wr = A.tw[2 * k], wi = A.tw[2 * k + 1], br = vr[(size_t)(i0 + h)], bi = vi[(size_t)(i0 + h)];
+                const double p0 = wr * br, p1 = wi * bi, p2 = wr * bi, p3 = wi * br;
+                const double tr = p0 - p1, ti = p2 + p3;
+                vr[(size_t)(i0 + h)] = vr[(size_t)i0] - tr;
+                vi[(size_t)(i0 + h)] = vi[(size_t)i0] - ti;
+                vr[(size_t)i0] = vr[(size_t)i0] + tr;
+                vi[(size_t)i0] = vi[(size_t)i0] + ti;
+            }
+        for (long long k = 0; k <= L / 2; ++k) {
+            const double pr = vr[(size_t)k] * vr[(size_t)k], pi = vi[(size_t)k] * vi[(size_t)k];
+            const double pw = pr + pi;
+            acc[k] = acc[k] + pw;
+        }
+    }
+    for (long long t = A.len > L ? A.len - L : 0; t < A.len; ++t) carry[(A.m0 + t) & (L - 1)] = yp[t * A.ny];
+}
+inline int meas_spectrum_launch(const MeasSpecArgs &A, void *) {
+    for (long long p = 0; p < A.n * A.nrows; ++p) meas_spectrum_chain(A, p);
+    return 0;
+}
+inline int meas_spectrum_zero(double *p, size_t count) {
+    std::fill(p, p + count, 0.0);
+    return 0;
+}
 inline int meas_fold_launch(const MeasFoldArgs &A, void *) {
     for (long long p = 0; p < A.n * A.nrows; ++p) meas_fold_chain(A, p);
     return 0;

@@ -67,6 +67,8 @@ ABI_SYMBOLS = [
     "acme_batch_set_source_multisine", "acme_batch_set_source_noise", "acme_batch_set_measurement_bins",
     "acme_batch_set_measurement_series", "acme_batch_get_measurement_series",
     "acme_batch_set_measurement_fold", "acme_batch_get_measurement_fold", "acme_batch_get_measurement_fold_sums",
+    "acme_batch_set_measurement_spectrum", "acme_batch_get_measurement_spectrum", "acme_batch_get_measurement_spectrum_sums",
+    "acme_batch_get_measurement_spectrum_table",
 ]
 
 SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE, SOURCE_NOISE = 1, 2, 3, 4, 5
@@ -197,6 +199,10 @@ class Library:
         L.acme_batch_set_measurement_fold.argtypes = [vp, C.c_longlong, lp]
         L.acme_batch_get_measurement_fold.argtypes = [vp, dp, lp, lp]
         L.acme_batch_get_measurement_fold_sums.argtypes = [vp, dp]
+        L.acme_batch_set_measurement_spectrum.argtypes = [vp, C.c_longlong, C.c_longlong, dp]
+        L.acme_batch_get_measurement_spectrum.argtypes = [vp, dp, lp, lp]
+        L.acme_batch_get_measurement_spectrum_sums.argtypes = [vp, dp]
+        L.acme_batch_get_measurement_spectrum_table.argtypes = [vp, dp, dp]
 
     def check(self, rc):
         if rc < 0:
@@ -373,6 +379,49 @@ class MeasurementFold:
         return cls(mean, np.concatenate([p.period for p in parts]), parts[0].count, parts[0].rows)
 
 
+class MeasurementSpectrum:
+    """What ``ModelRunner.measurement_spectrum()`` returns: Welch-averaged periodograms of the measured window.  ``power``
+    (N, nrows, nfft / 2 + 1): the mean over ``segments`` segments of |FFT(w x)|^2, unscaled (NaN while ``segments`` is 0;
+    ``raw``: the sums); ``count`` the samples measured, ``rows`` the measured output rows, ``window`` the nfft window
+    values, ``hop`` the segments' spacing."""
+
+    def __init__(self, power, segments, count, rows, window, hop):
+        self.power, self.segments, self.count, self.rows = power, int(segments), int(count), tuple(rows)
+        self.window, self.hop = np.asarray(window, dtype=np.float64), int(hop)
+
+    @property
+    def nfft(self):
+        return len(self.window)
+
+    def freqs(self, fs):
+        """the bins' frequencies, k fs / nfft"""
+        return np.arange(self.nfft // 2 + 1) * (float(fs) / self.nfft)
+
+    def psd(self, fs):
+        """the one-sided power spectral density, ``power / (fs sum w^2)``, doubled except at DC and Nyquist (what
+        ``scipy.signal.welch(..., scaling="density", detrend=False)`` reports)"""
+        d = self.power / (float(fs) * np.sum(self.window ** 2))
+        d[..., 1:-1] *= 2.0
+        return d
+
+    def band_power(self, fs, f_lo, f_hi):
+        """the power in f_lo <= f <= f_hi: the density's bins there times the bin width fs / nfft -- (N, nrows)"""
+        f = self.freqs(fs)
+        return self.psd(fs)[..., (f >= f_lo) & (f <= f_hi)].sum(axis=-1) * (float(fs) / self.nfft)
+
+    def amplitude(self):
+        """the amplitude of a line that sits on a bin, ``2 sqrt(power) / sum w`` (DC and Nyquist read twice their value)"""
+        return 2.0 * np.sqrt(self.power) / np.sum(self.window)
+
+    @classmethod
+    def concatenate(cls, parts):
+        a = parts[0]
+        if any((p.segments, p.count, p.rows, p.hop) != (a.segments, a.count, a.rows, a.hop) or not np.array_equal(p.window, a.window)
+               for p in parts):
+            raise ValueError("the shards' spectra differ in their segments, sample counts, measured rows or windows")
+        return cls(np.concatenate([p.power for p in parts]), a.segments, a.count, a.rows, a.window, a.hop)
+
+
 def measure_spec(ny, start=0, length=0, f0=None, harmonics=0, rows=None):
     """((start, length, f_num, f_den, harmonics, row mask), measured rows) -- acme_batch_set_measurement's arguments -- from
     ``ModelRunner.set_measurement``'s: ``f0`` a Fraction of fs or
@@ -491,6 +540,7 @@ class ModelRunner:
         self._meas = None               # measurement: (harmonics, measured rows) while armed
         self._series = (0, None)        # (the armed start, (win, hop, windows) of a series or None)
         self._fold = False              # a fold is set on the armed measurement
+        self._spectrum = None           # (nfft, hop) of the spectrum set on the armed measurement
         self._sources = {}              # input row -> kind, while the row has a source
         self._sine = {}                 # input row -> (f_den, f_num as armed) of its sine source
         self._progress_cb = None
@@ -582,6 +632,7 @@ class ModelRunner:
         self._meas = (int(harmonics), rows)
         self._series = (int(start), None)
         self._fold = False
+        self._spectrum = None
         return self
 
     def set_measurement_bins(self, coef, start=0, length=0, rows=None, f_den=None, f_num=None, tones_from_source=None):
@@ -617,6 +668,7 @@ class ModelRunner:
         self._meas = (ca.shape[0], rows)
         self._series = (int(start), None)
         self._fold = False
+        self._spectrum = None
         return self
 
     def measurement_plan(self):
@@ -638,6 +690,7 @@ class ModelRunner:
         self._meas = None
         self._series = (0, None)
         self._fold = False
+        self._spectrum = None
         return self
 
     def set_measurement_series(self, win, hop=None, windows=1):
@@ -712,6 +765,55 @@ class ModelRunner:
         else:
             self.lib.check(self.lib.L.acme_batch_get_measurement_fold(self.h, _dp(out), None, None))
         return MeasurementFold(out, period, count.value, rows)
+
+    def set_measurement_spectrum(self, nfft, hop=None, window="hann"):
+        """Welch-averaged periodograms of the armed measurement's window (``acme_batch_set_measurement_spectrum``): segments
+        of ``nfft`` samples (a power of two, 64 ... 4096), one every ``hop`` (None: ``nfft // 2``), each multiplied by
+        ``window`` -- "hann" (periodic), "rect" or ``nfft`` values --, transformed on the device and |X_k|^2 accumulated per
+        instance, measured row and bin.  Needs an armed measurement (any form, any window) that has not been fed yet; not
+        together with a series; ``measurement_spectrum`` reads it."""
+        if self._meas is None:
+            raise AcmeError("no measurement is armed")
+        nfft = int(nfft)
+        hop = nfft // 2 if hop is None else int(hop)
+        if isinstance(window, str):
+            if window == "hann":
+                w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(max(nfft, 0)) / max(nfft, 1))
+            elif window == "rect":
+                w = None
+            else:
+                raise ValueError(f"window {window!r}: \"hann\", \"rect\" or an array of nfft values")
+        else:
+            w = np.ascontiguousarray(window, dtype=np.float64)
+            if w.shape != (nfft,):
+                raise DimensionMismatch(f"the window needs {nfft} values")
+        self.lib.check(self.lib.L.acme_batch_set_measurement_spectrum(self.h, nfft, hop, None if w is None else _dp(w)))
+        self._spectrum = (nfft, hop)
+        return self
+
+    def measurement_spectrum_table(self):
+        """(w (nfft,), tw (nfft / 2, 2)): the window and the twiddles (cos, -sin)(2 pi k / nfft) the kernel uses
+        (``acme_batch_get_measurement_spectrum_table``)"""
+        if self._meas is None or self._spectrum is None:
+            raise AcmeError("no measurement spectrum is set")
+        nfft = self._spectrum[0]
+        w, tw = np.empty(nfft), np.empty((nfft // 2, 2))
+        self.lib.check(self.lib.L.acme_batch_get_measurement_spectrum_table(self.h, _dp(w), _dp(tw)))
+        return w, tw
+
+    def measurement_spectrum(self, raw=False):
+        """the spectrum so far (``acme_batch_get_measurement_spectrum``): a ``MeasurementSpectrum``.  ``raw``: ``power`` holds
+        the bins' sums, undivided (``acme_batch_get_measurement_spectrum_sums``; the tests pin the chains on them)."""
+        if self._meas is None or self._spectrum is None:
+            raise AcmeError("no measurement spectrum is set")
+        nfft, hop = self._spectrum
+        rows = self._meas[1]
+        seg, count = C.c_longlong(0), C.c_longlong(0)
+        out = np.empty((self.n, len(rows), nfft // 2 + 1))
+        self.lib.check(self.lib.L.acme_batch_get_measurement_spectrum(self.h, None if raw else _dp(out), C.byref(seg), C.byref(count)))
+        if raw:
+            self.lib.check(self.lib.L.acme_batch_get_measurement_spectrum_sums(self.h, _dp(out)))
+        return MeasurementSpectrum(out, seg.value, count.value, rows, self.measurement_spectrum_table()[0], hop)
 
     def reset_measurement(self):
         """zero the accumulators and restart the window's clock (``acme_batch_reset_measurement``)"""
@@ -1365,6 +1467,17 @@ class MultiDeviceRunner:
     def measurement_fold(self, raw=False):
         """the shards' ``MeasurementFold`` results, concatenated along the instances (``raw`` as ``ModelRunner``'s)"""
         return MeasurementFold.concatenate([r.measurement_fold(raw) for r in self.runners if r is not None])
+
+    def set_measurement_spectrum(self, nfft, hop=None, window="hann"):
+        """``ModelRunner.set_measurement_spectrum`` on every device's batch"""
+        for r in self.runners:
+            if r is not None:
+                r.set_measurement_spectrum(nfft, hop, window)
+        return self
+
+    def measurement_spectrum(self, raw=False):
+        """the shards' ``MeasurementSpectrum`` results, concatenated along the instances (``raw`` as ``ModelRunner``'s)"""
+        return MeasurementSpectrum.concatenate([r.measurement_spectrum(raw) for r in self.runners if r is not None])
 
     def measure(self, u=None, check=True, T=None):
         """``run`` with y = NULL on every device (``u``: (N, T, nu), the ABI's layout); only the measurements are fed.

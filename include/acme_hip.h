@@ -367,6 +367,52 @@ int acme_batch_get_measurement_fold(acme_batch *b, double *out, long long *perio
 /* the same slots undivided: out[N][nrows][Pmax] (not NULL), out[i][j][s] = fold[i][j][s], the chain's sum itself (the tests pin
  * it with ==; sums of separate runs can be added before dividing); the slots that read NaN above read NaN here. */
 int acme_batch_get_measurement_fold_sums(acme_batch *b, double *out);
+/* A SPECTRUM of the window (Welch's method): the armed measurement (any of the three forms, no sample fed since arming or the
+ * last reset) also cuts its window [start, start + length) into overlapping segments of L samples, one every `hop` samples,
+ * multiplies each by the window w, transforms it with an fp64 FFT on the device and accumulates |X_k|^2 over the segments, per
+ * instance, measured row and bin k = 0 ... L / 2 -- the estimator for signals that are not periodic: the output of a
+ * noise-driven run, THD+N, the noise floor between the harmonics, N x nrows x (L / 2 + 1) doubles in place of y [N][T][ny].
+ *   L     a power of two, ACME_MIN_SPECTRUM <= L <= ACME_MAX_SPECTRUM
+ *   hop   1 <= hop <= L
+ *   w     HOST array of L finite values (copied by the call), or NULL: all 1.0
+ * Segments: with m = n - start the window-relative sample number, segment s = 0, 1, ... covers m in [s hop, s hop + L).  It
+ * contributes once all its samples have been fed and lie inside the window: after `count` samples
+ * segments = count >= L ? (count - L) / hop + 1 : 0; samples beyond the last complete segment contribute nothing.
+ * Arithmetic, per segment and pair -- every operation rounded on its own, NO fused multiply-add anywhere:
+ *   1. x_j = w[j] y[s hop + j], one product; the imaginary part is 0.
+ *   2. X = FFT_L(x), the radix-2 decimation-in-time transform: load in bit-reversed order; stages q = 1 ... log2 L with
+ *      half-size h = 2^(q-1); a butterfly on a = v[i], b = v[i + h] with (wr, wi) = tw[(i mod h) (L / 2h)] computes
+ *      tr = wr br - wi bi, ti = wr bi + wi br (two products and one subtraction / addition each) and stores v[i] = a + t,
+ *      v[i + h] = a - t.
+ *   3. for k = 0 ... L / 2: acc[k] += (Xr Xr + Xi Xi), ONE chain per bin in segment order from 0.0.
+ * This fixes the VALUES, not the data flow (stages kept in registers, products with an exact 0.0 or 1.0 skipped and any
+ * mapping to lanes give the same bits; signed zeros may differ).  tw[k] approximates (cos 2 pi k / L, -sin 2 pi k / L), k < L / 2,
+ * made once at arming, each entry within 1.5 x 2^-53 of the exact value and exactly (1, 0) at k = 0, (0, -1) at k = L / 4.
+ * The sums depend on nothing but the run's samples: chunk, slice and call boundaries, host or device memory, the entry point
+ * (acme_batch_run, _run_const, _run_async, _run_sources, device pointers), y stored or NULL, the oversampling factor and
+ * ACME_OS_SLICE change none of their bits.  The measurement's own accumulators and launches are what they are without a
+ * spectrum; the spectrum takes one more kernel per chunk of the window and N nrows (L + L / 2 + 1) doubles of device memory
+ * (the accumulators and a carry of the window's L most recent samples per pair).  A fold and a spectrum may be set together.
+ * The kernel of a chunk transforms every segment that ends in the chunk, about chunk / hop per pair (a chunk is at most 4096
+ * samples) in ONE launch: the cost grows as L log2 L / hop per sample, and a hop far below L / 8 on a wide batch makes that launch
+ * long (hop = 1 at L = 4096 is 4096 transforms of 4096 points per pair and chunk).  Keep hop >= L / 8 on wide batches; smaller
+ * hops are accepted and correct.
+ * ACME_ERR_INVALID: no measurement armed, samples already fed, L not a power of two or out of range, hop out of range, a
+ * non-finite window value.  ACME_ERR_UNSUPPORTED together with a series, whichever is set first.  Setting a spectrum again
+ * replaces the earlier one.  _reset_measurement zeroes the sums and the carried samples and keeps L, hop, w and the table;
+ * arming any form or _clear_measurement removes the spectrum; acme_batch_set_matrices carries it with the accumulators.  A
+ * batch without a spectrum launches and allocates what it always did. */
+#define ACME_MIN_SPECTRUM 64
+#define ACME_MAX_SPECTRUM 4096
+int acme_batch_set_measurement_spectrum(acme_batch *b, long long L, long long hop, const double *w /* host [L], NULL: all 1.0 */);
+/* the spectrum so far: out[N][nrows][L / 2 + 1] (may be NULL) = acc / segments, NaN everywhere while segments == 0; *segments,
+ * *count: complete segments and samples measured (may be NULL).  No scaling by the sample rate or the window's power is
+ * applied.  ACME_ERR_INVALID without a spectrum.  Joins a pending acme_batch_run_async and synchronises the device. */
+int acme_batch_get_measurement_spectrum(acme_batch *b, double *out, long long *segments, long long *count);
+/* the same bins undivided: out[N][nrows][L / 2 + 1] (not NULL), the chains' sums themselves (NaN while segments == 0) */
+int acme_batch_get_measurement_spectrum_sums(acme_batch *b, double *out);
+/* the window w[L] and the table tw[L / 2][2] the kernel uses (either may be NULL) */
+int acme_batch_get_measurement_spectrum_table(acme_batch *b, double *w, double *tw);
 /* switch the measurement off (y = NULL is refused again) */
 int acme_batch_clear_measurement(acme_batch *b);
 /* zero the accumulators and restart the window's clock (the armed parameters stay) */

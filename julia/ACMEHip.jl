@@ -38,7 +38,7 @@ export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host
        MeasureSpec, Measurement, set_measurement!, clear_measurement!, reset_measurement!, measurement, measurement_plan, measure!,
        set_source!, clear_source!, source_clock, source_clock!, run_sources!, render_sources,
        set_source_multisine!, set_source_noise!, set_measurement_bins!, set_measurement_series!, measurement_series,
-       set_measurement_fold!, measurement_fold
+       set_measurement_fold!, measurement_fold, set_measurement_spectrum!, measurement_spectrum
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
 
@@ -51,6 +51,8 @@ const ACME_MEM_HOST, ACME_MEM_DEVICE = Cint(0), Cint(1)
 const ACME_MAX_OVERSAMPLING = 16
 const ACME_MAX_HARMONICS = 32
 const ACME_MAX_SERIES_WINDOWS = 1048576
+const ACME_MIN_SPECTRUM = 64
+const ACME_MAX_SPECTRUM = 4096
 const ACME_SOURCE_CONST, ACME_SOURCE_SINE, ACME_SOURCE_TABLE, ACME_SOURCE_MULTISINE = Cint(1), Cint(2), Cint(3), Cint(4)
 const ACME_SOURCE_NOISE = Cint(5)
 const ACME_NOISE_UNIFORM, ACME_NOISE_GAUSSIAN = Cint(0), Cint(1)
@@ -218,6 +220,7 @@ mutable struct BatchRunner
     showprogress::Bool
     meas::Any                         # the armed MeasureSpec (nothing: none)
     sources::Set{Int}                 # the input rows (1-based) that have a source
+    spectrum::Int                     # nfft of the spectrum set on the armed measurement (0: none)
 end
 
 # @showprogress of run!(runner, y, u) (src/ACME.jl:587-604,653): the library reports after every time slice of a
@@ -236,7 +239,7 @@ function BatchRunner(model::DiscreteModel, n::Integer; device::Integer=-1,
     b = Ref{Ptr{Cvoid}}()
     check(ccall((:acme_batch_create, lib), Cint, (Ptr{Cvoid}, Clonglong, Ref{AcmeOptions}, Ref{Ptr{Cvoid}}),
                 mh.h, n, opts, b))
-    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress, nothing, Set{Int}())
+    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress, nothing, Set{Int}(), 0)
     finalizer(r -> ccall((:acme_batch_destroy, lib), Cvoid, (Ptr{Cvoid},), r.h), r)
     if showprogress
         cb = @cfunction(progress_trampoline, Cvoid, (Ptr{Cvoid}, Clonglong, Clonglong))
@@ -478,6 +481,7 @@ function set_measurement!(r::BatchRunner, spec::MeasureSpec)
                 (Ptr{Cvoid}, Clonglong, Clonglong, Clonglong, Clonglong, Cint, Culonglong),
                 r.h, spec.start, spec.length, spec.f_num, spec.f_den, spec.harmonics, spec.rows))
     r.meas = spec
+    r.spectrum = 0
     return r
 end
 function set_measurement!(r::BatchRunner; f_den=nothing, f_num=nothing, kwargs...)
@@ -500,6 +504,7 @@ function set_measurement!(r::BatchRunner, spec::MeasureSpec, f_den::Int64, f_num
                 (Ptr{Cvoid}, Clonglong, Clonglong, Clonglong, Ptr{Clonglong}, Cint, Culonglong),
                 r.h, spec.start, spec.length, f_den, f_num, spec.harmonics, spec.rows))
     r.meas = spec
+    r.spectrum = 0
     return r
 end
 
@@ -523,6 +528,7 @@ function set_measurement_bins!(r::BatchRunner, coef::Matrix{<:Integer}, f_den::I
                 (Ptr{Cvoid}, Clonglong, Clonglong, Clonglong, Cint, Ptr{Clonglong}, Cint, Ptr{Cint}, Culonglong),
                 r.h, spec.start, spec.length, f_den, tones, f_num, bins, c, spec.rows))
     r.meas = spec
+    r.spectrum = 0
     return r
 end
 
@@ -548,6 +554,7 @@ end
 function clear_measurement!(r::BatchRunner)
     check(ccall((:acme_batch_clear_measurement, lib), Cint, (Ptr{Cvoid},), r.h))
     r.meas = nothing
+    r.spectrum = 0
     return r
 end
 
@@ -644,6 +651,51 @@ function measurement_fold(r::BatchRunner; sums::Bool=false)
                     r.h, mean, C_NULL, C_NULL))
     end
     return (mean=mean, period=period, count=count[])
+end
+
+"""
+    set_measurement_spectrum!(runner, nfft; hop=nfft ÷ 2, window=nothing)
+
+Welch-averaged periodograms of the armed measurement's window (`acme_batch_set_measurement_spectrum`): segments of `nfft`
+samples (a power of two, 64 ... 4096), one every `hop`, each multiplied by `window::Vector{Float64}` (`nothing`: the
+periodic Hann window; `:rect`: all ones), transformed on the device and |X_k|^2 accumulated per instance, measured row and
+bin.  Needs an armed measurement that has not been fed yet; not together with a series.
+"""
+function set_measurement_spectrum!(r::BatchRunner, nfft::Integer; hop::Integer=nfft ÷ 2, window=nothing)
+    r.meas === nothing && error("no measurement is armed")
+    w = window === :rect ? Float64[] :
+        window === nothing ? [0.5 - 0.5 * cos(2pi * j / nfft) for j in 0:nfft-1] : convert(Vector{Float64}, window)
+    window === :rect || length(w) == nfft || throw(DimensionMismatch("the window needs $nfft values"))
+    GC.@preserve w check(ccall((:acme_batch_set_measurement_spectrum, lib), Cint,
+                (Ptr{Cvoid}, Clonglong, Clonglong, Ptr{Cdouble}), r.h, nfft, hop, ptr_or_null(w)))
+    r.spectrum = Int(nfft)
+    return r
+end
+
+"""
+    measurement_spectrum(runner; sums=false) -> (power, segments, count, window, table)
+
+The spectrum so far (`acme_batch_get_measurement_spectrum`): `power` is (nfft ÷ 2 + 1) x nrows x N, the mean over `segments`
+segments of |FFT(w x)|^2, unscaled (NaN while `segments == 0`); `sums=true`: the bins' sums, undivided
+(`acme_batch_get_measurement_spectrum_sums`).  `window` (nfft) and `table` (2 x nfft ÷ 2: cos, -sin of 2 pi k / nfft) are
+what the kernel uses (`acme_batch_get_measurement_spectrum_table`).
+"""
+function measurement_spectrum(r::BatchRunner; sums::Bool=false)
+    spec = r.meas
+    (spec === nothing || r.spectrum == 0) && error("no measurement spectrum is set")
+    ny = ACME.ny(r.model)
+    nrows = spec.rows == 0 ? min(ny, 64) : count_ones(spec.rows)
+    nfft = r.spectrum
+    segments, count = Ref{Clonglong}(0), Ref{Clonglong}(0)
+    power = Array{Float64,3}(undef, nfft ÷ 2 + 1, nrows, r.n)       # the ABI's [N][nrows][nfft / 2 + 1]
+    check(ccall((:acme_batch_get_measurement_spectrum, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Clonglong}, Ptr{Clonglong}),
+                r.h, power, segments, count))
+    if sums
+        check(ccall((:acme_batch_get_measurement_spectrum_sums, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), r.h, power))
+    end
+    window, table = Vector{Float64}(undef, nfft), Matrix{Float64}(undef, 2, nfft ÷ 2)
+    check(ccall((:acme_batch_get_measurement_spectrum_table, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), r.h, window, table))
+    return (power=power, segments=segments[], count=count[], window=window, table=table)
 end
 
 """
