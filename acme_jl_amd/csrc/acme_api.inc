@@ -175,6 +175,15 @@ struct acme_batch {
         double *d_spec_w = nullptr, *d_spec_tw = nullptr;
         double *d_spec_acc = nullptr;            // [N nrows][L / 2 + 1] sums of |X_k|^2, from 0.0
         double *d_spec_carry = nullptr;          // [N nrows][L]: the window's most recent samples, sample m at m mod L
+        // cross-spectrum (acme_batch_set_measurement_cross): the spectrum's segments of input row cross_in and the measured
+        // rows, packed into one complex transform per pair
+        bool cross = false;
+        int cross_in = 0;
+        long long cross_L = 0, cross_hop = 0;
+        std::vector<double> cross_w, cross_tw;   // [L] the window, [L / 2][2] the twiddles, as the device has them
+        double *d_cross_w = nullptr, *d_cross_tw = nullptr;
+        double *d_cross_acc = nullptr;           // [N nrows][4][L / 2 + 1] sums of |X|^2, |Y|^2, Re and Im conj(X) Y, from 0.0
+        double *d_cross_carry = nullptr;         // [N nrows][2][L]: the most recent samples of x and of y, sample m at m mod L
     } meas;
     // Input rows generated on the device (acme_batch_set_source_*, acme_source.h): the rows' descriptions and per-instance
     // parameters in device memory, the source clock
@@ -788,6 +797,7 @@ static void meas_release(acme_batch::Measurement &M) {
     (void)be::dfree(M.d_kbin_g);
     (void)be::dfree(M.d_fold_per); (void)be::dfree(M.d_fold);
     (void)be::dfree(M.d_spec_w); (void)be::dfree(M.d_spec_tw); (void)be::dfree(M.d_spec_acc); (void)be::dfree(M.d_spec_carry);
+    (void)be::dfree(M.d_cross_w); (void)be::dfree(M.d_cross_tw); (void)be::dfree(M.d_cross_acc); (void)be::dfree(M.d_cross_carry);
     M = acme_batch::Measurement{};
 }
 
@@ -1441,8 +1451,9 @@ static int os_grow(double **p, size_t *cap, size_t bytes) {
     return ACME_OK;
 }
 // the measurement step of n base-rate output samples (instance i, sample t, row r at y[(i * pitch + t) * ny + r]) that follow
-// the meas.pos samples since arming: the part inside the window [start, start + length), chunk by chunk
-static int meas_step(acme_batch *b, const double *y, long long n, long long pitch, be::stream_t st) {
+// the meas.pos samples since arming: the part inside the window [start, start + length), chunk by chunk.  u: the same n samples
+// of the base-rate input rows, complete (instance i, sample t, row r at u[(i * upitch + t) * nu + r]); the cross-spectrum reads it
+static int meas_step(acme_batch *b, const double *y, long long n, long long pitch, const double *u, long long upitch, be::stream_t st) {
     acme_batch::Measurement &M = b->meas;
     const long long end = M.W ? M.start + (M.W - 1) * M.hop + M.win : M.length ? M.start + M.length : LLONG_MAX;
     const long long lo = M.pos > M.start ? M.pos : M.start, hi = M.pos + n < end ? M.pos + n : end;
@@ -1477,6 +1488,12 @@ static int meas_step(acme_batch *b, const double *y, long long n, long long pitc
                            M.spec_L, M.spec_hop, A.ny, M.nrows, {}};
             memcpy(G.row, M.row, sizeof(G.row));
             HIPCHK(meas_spectrum_launch(G, st));
+        }
+        if (M.cross) {  // ... and those segments of the input row beside the measured rows
+            MeasCrossArgs G{{y, M.d_cross_acc, M.d_cross_carry, M.d_cross_w, M.d_cross_tw, b->N, len, pitch, s - M.pos, s - M.start,
+                             M.cross_L, M.cross_hop, A.ny, M.nrows, {}}, u, upitch, b->P.actual.nu, M.cross_in};
+            memcpy(G.S.row, M.row, sizeof(G.S.row));
+            HIPCHK(meas_cross_launch(G, st));
         }
     }
     M.pos += n;
@@ -1561,7 +1578,7 @@ static int run_os(acme_batch *b, const double *u, const double *u_const, unsigne
             O.fresh = false;
         }
         if (scatter) HIPCHK(src_launch_copy(SrcCopyArgs{y + (size_t)s * TS * ny, dst, (long long)N, n, T, ny}, st));
-        return M.on ? meas_step(b, dst, n, ypitch, st) : ACME_OK;
+        return M.on ? meas_step(b, dst, n, ypitch, src, pitch, st) : ACME_OK;
     };
     if (!host) {
         for (long long s = 0; s < ns; ++s) {
@@ -2144,6 +2161,11 @@ static int meas_zero(acme_batch *b) {
         HIPCHK(meas_spectrum_zero(M.d_spec_carry, P * (size_t)M.spec_L));
         HIPCHK(be::device_sync());
     }
+    if (M.cross) {      // the same of the cross-spectrum (in_row stays too)
+        HIPCHK(meas_cross_zero(M.d_cross_acc, P * 4 * (size_t)(M.cross_L / 2 + 1)));
+        HIPCHK(meas_cross_zero(M.d_cross_carry, P * 2 * (size_t)M.cross_L));
+        HIPCHK(be::device_sync());
+    }
     M.pos = 0;
     return ACME_OK;
 }
@@ -2315,6 +2337,7 @@ int acme_batch_set_measurement_series(acme_batch *b, long long win, long long ho
     if (!M.on) return fail(ACME_ERR_INVALID, "measurement series: no measurement is armed");
     if (M.fold) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a fold (a fold per window is not supported)");
     if (M.spec) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a spectrum (a spectrum per window is not supported)");
+    if (M.cross) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a cross-spectrum (a cross-spectrum per window is not supported)");
     if (M.length != 0) return fail(ACME_ERR_INVALID, "measurement series: the armed measurement's length must be 0 (the series sets the windows)");
     if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement series: samples have been fed since arming (arm or reset the measurement first)");
     if (win < 1) return fail(ACME_ERR_INVALID, "measurement series: win must be >= 1");
@@ -2532,6 +2555,88 @@ int acme_batch_get_measurement_spectrum_table(acme_batch *b, double *w, double *
     if (!M.on || !M.spec) return fail(ACME_ERR_INVALID, "no measurement spectrum is set");
     if (w) memcpy(w, M.spec_w.data(), sizeof(double) * M.spec_w.size());
     if (tw) memcpy(tw, M.spec_tw.data(), sizeof(double) * M.spec_tw.size());
+    return ACME_OK;
+}
+
+int acme_batch_set_measurement_cross(acme_batch *b, int in_row, long long L, long long hop, const double *w) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    acme_batch::Measurement &M = b->meas;
+    if (!M.on) return fail(ACME_ERR_INVALID, "measurement cross: no measurement is armed");
+    if (M.W) return fail(ACME_ERR_UNSUPPORTED, "measurement cross: the measurement has a series of windows (a cross-spectrum per window is not supported)");
+    if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement cross: samples have been fed since arming (arm or reset the measurement first)");
+    const int nu = b->P.actual.nu;
+    if (nu == 0) return fail(ACME_ERR_INVALID, "measurement cross: the model has no input row (nu = 0)");
+    if (in_row < 0 || in_row >= nu) return fail(ACME_ERR_INVALID, "measurement cross: in_row is outside 0 ... nu - 1 = " + std::to_string(nu - 1));
+    if (L < MEAS_MIN_SPECTRUM || L > MEAS_MAX_SPECTRUM || (L & (L - 1)) != 0)
+        return fail(ACME_ERR_INVALID, "measurement cross: L must be a power of two, " + std::to_string(MEAS_MIN_SPECTRUM) + " ... " +
+                                          std::to_string(MEAS_MAX_SPECTRUM));
+    if (hop < 1 || hop > L) return fail(ACME_ERR_INVALID, "measurement cross: hop is outside 1 ... L");
+    std::vector<double> win((size_t)L, 1.0);
+    for (long long j = 0; w && j < L; ++j) {
+        if (!std::isfinite(w[j])) return fail(ACME_ERR_INVALID, "measurement cross: w[" + std::to_string(j) + "] is not finite");
+        win[(size_t)j] = w[j];
+    }
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    (void)be::dfree(M.d_cross_w); (void)be::dfree(M.d_cross_tw); (void)be::dfree(M.d_cross_acc); (void)be::dfree(M.d_cross_carry);
+    M.d_cross_w = M.d_cross_tw = M.d_cross_acc = M.d_cross_carry = nullptr; // (a cross-spectrum set again replaces the earlier one)
+    M.cross = false;
+    std::vector<double> tw = spectrum_table(L);
+    const size_t pairs = (size_t)b->N * (size_t)M.nrows;
+    HIPCHK(be::dmalloc((void **)&M.d_cross_w, sizeof(double) * (size_t)L));
+    HIPCHK(be::dmalloc((void **)&M.d_cross_tw, sizeof(double) * (size_t)L));
+    HIPCHK(be::dmalloc((void **)&M.d_cross_acc, sizeof(double) * pairs * 4 * (size_t)(L / 2 + 1)));
+    HIPCHK(be::dmalloc((void **)&M.d_cross_carry, sizeof(double) * pairs * 2 * (size_t)L));
+    HIPCHK(be::copy_h2d(M.d_cross_w, win.data(), sizeof(double) * (size_t)L));
+    HIPCHK(be::copy_h2d(M.d_cross_tw, tw.data(), sizeof(double) * (size_t)L));
+    HIPCHK(meas_cross_zero(M.d_cross_acc, pairs * 4 * (size_t)(L / 2 + 1)));
+    HIPCHK(meas_cross_zero(M.d_cross_carry, pairs * 2 * (size_t)L));
+    HIPCHK(be::device_sync());
+    M.cross_w = std::move(win);
+    M.cross_tw = std::move(tw);
+    M.cross_L = L;
+    M.cross_hop = hop;
+    M.cross_in = in_row;
+    M.cross = true;
+    return ACME_OK;
+}
+
+static int get_measurement_cross(acme_batch *b, double *out, long long *segments, long long *count, bool sums) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const acme_batch::Measurement &M = b->meas;
+    if (!M.on || !M.cross) return fail(ACME_ERR_INVALID, "no measurement cross-spectrum is set");
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    const long long end = M.length ? M.start + M.length : LLONG_MAX;
+    const long long cnt = (M.pos < end ? M.pos : end) - M.start, c = cnt > 0 ? cnt : 0;
+    const long long S = c >= M.cross_L ? (c - M.cross_L) / M.cross_hop + 1 : 0;
+    if (count) *count = c;
+    if (segments) *segments = S;
+    if (!out) return ACME_OK;
+    const size_t total = (size_t)b->N * M.nrows * 4 * (size_t)(M.cross_L / 2 + 1);
+    if (total) HIPCHK(be::copy_d2h(out, M.d_cross_acc, sizeof(double) * total));    // (the accumulators' layout is the result's)
+    for (size_t k = 0; k < total; ++k) out[k] = S == 0 ? NAN : sums ? out[k] : out[k] / (double)S;
+    return ACME_OK;
+}
+
+int acme_batch_get_measurement_cross(acme_batch *b, double *out, long long *segments, long long *count) {
+    return get_measurement_cross(b, out, segments, count, false);
+}
+
+int acme_batch_get_measurement_cross_sums(acme_batch *b, double *out) {
+    if (b && !out) return fail(ACME_ERR_INVALID, "measurement cross sums: out is null");
+    return get_measurement_cross(b, out, nullptr, nullptr, true);
+}
+
+int acme_batch_get_measurement_cross_table(acme_batch *b, double *w, double *tw) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const acme_batch::Measurement &M = b->meas;
+    if (!M.on || !M.cross) return fail(ACME_ERR_INVALID, "no measurement cross-spectrum is set");
+    if (w) memcpy(w, M.cross_w.data(), sizeof(double) * M.cross_w.size());
+    if (tw) memcpy(tw, M.cross_tw.data(), sizeof(double) * M.cross_tw.size());
     return ACME_OK;
 }
 

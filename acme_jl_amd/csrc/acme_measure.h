@@ -72,6 +72,14 @@
 // chunk (acme_meas_spectrum_kernel<log2 L>): a block of 256 lanes per pair, the vector in LDS, two stages a pass in
 // registers; the emulator walks meas_spectrum_chain, the contract as a plain loop.
 //
+// CROSS-SPECTRUM (acme_batch_set_measurement_cross): the spectrum's segments of two real signals per pair -- x, one input row
+// of the model as the run sees it at the base rate, and y, the measured row.  z = w x + i w y goes through ONE complex
+// transform of the spectrum's (nothing assumed zero); X_k = (Z_k + conj Z_{L-k}) / 2 and Y_k = (Z_k - conj Z_{L-k}) / 2i are
+// split off and four chains per bin accumulate |X|^2, |Y|^2 and the two parts of conj(X) Y in segment order from 0.0.  The
+// accumulators are [N nrows][4][L / 2 + 1]; the carry is [N nrows][2][L], a ring of x and a ring of y per PAIR (a ring of x
+// shared by an instance's rows would be rewritten by one row's block while another still reads it).  One more kernel per
+// chunk (acme_meas_cross_kernel<log2 L>), the spectrum kernel's shape; the emulator walks meas_cross_chain.
+//
 // The per-element functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with g++).
 #pragma once
@@ -246,6 +254,17 @@ ACME_HD inline void meas_spec_segments(long long m0, long long len, long long L,
     *lo = m0 >= L ? (m0 - L + hop) / hop : 0;           // s hop + L - 1 >= m0
     *hi = m0 + len >= L ? (m0 + len - L) / hop : -1;    // s hop + L - 1 < m0 + len
 }
+
+// cross-spectrum: the spectrum's segments of TWO real signals per pair, x = input row in_row as the run sees it at the base
+// rate and y = the measured row, packed into one complex transform.  S is the spectrum's argument block with
+// acc [n * nrows][4][L / 2 + 1] (the planes xx, yy, re, im, from 0.0) and carry [n * nrows][2][L] (the ring of x, then the
+// ring of y: sample m at m mod L)
+struct MeasCrossArgs {
+    MeasSpecArgs S;
+    const double *u;            // instance i, sample t of the chunk at u[(i * upitch + t0 + t) * nu + in_row]
+    long long upitch;
+    int nu, in_row;
+};
 
 // Every operation of the spectrum is rounded on its own: no fused multiply-add (the compilers contract by default)
 #if defined(__clang__)
@@ -862,7 +881,152 @@ __global__ __launch_bounds__(256) void acme_meas_spectrum_kernel(acme::MeasSpecA
     // the chunk's last min(len, L) samples into the ring (every read of it lies before a barrier above)
     for (long long t = (A.len > L ? A.len - L : 0) + tid; t < A.len; t += 256) carry[(A.m0 + t) & (L - 1)] = yp[t * A.ny];
 }
+
+// cross-spectrum: the spectrum kernel's shape -- a block of 256 lanes per pair, the padded re / im arrays, two stages a pass,
+// G = 1024 / L segments side by side -- on z = w x + i w y: the load fills BOTH arrays (the real part from the input row, the
+// imaginary part from the measured row, both in bit-reversed order), so the first pass reads the imaginary array like every
+// other.  Behind the passes the owner of bin k = lane + 256 b reads Z at k and at n = (L - k) mod L, splits X and Y off and
+// adds into four sums per bin, held in registers over the chunk.  The reads at k ascend with the lane and are free of bank
+// conflicts as the spectrum's; the reads at n descend: the 32 lanes of a half wave (k = 32 a ... 32 a + 31) cover the padded
+// positions of n = L - 32 a - 31 ... L - 32 a, 33 consecutive doubles less the one pad between the last two, so lanes 0 and 31
+// of every half meet in one bank -- a two-way conflict on each of the two descending reads, none elsewhere.  Both rings are
+// read by the loads only, every load is followed by a barrier of the block, and the rewrite comes behind the last of them.
+template <int LOG2L>
+__global__ __launch_bounds__(256) void acme_meas_cross_kernel(acme::MeasCrossArgs C) {
+    ACME_NO_CONTRACT
+    using namespace acme;
+    constexpr int L = 1 << LOG2L, Q = L / 4, G = Q >= 256 ? 1 : 256 / Q, PITCH = L + L / 32, NB = (L / 2 + 256) / 256, NK = L / 2 + 1;
+    __shared__ double sre[G * PITCH], sim[G * PITCH];
+    const MeasSpecArgs &A = C.S;
+    const int tid = threadIdx.x;
+    const long long p = blockIdx.x, i = p / A.nrows;
+    const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    const double *up = C.u + (i * C.upitch + A.t0) * C.nu + C.in_row;
+    double *cx = A.carry + p * (2 * L), *cy = cx + L, *acc = A.acc + p * (4 * NK);
+    long long s_lo, s_hi;
+    meas_spec_segments(A.m0, A.len, L, A.hop, &s_lo, &s_hi);
+    double axx[NB], ayy[NB], are[NB], aim[NB];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const bool own = s_lo <= s_hi && tid + 256 * b <= L / 2;
+        axx[b] = own ? acc[tid + 256 * b] : 0.0;
+        ayy[b] = own ? acc[NK + tid + 256 * b] : 0.0;
+        are[b] = own ? acc[2 * NK + tid + 256 * b] : 0.0;
+        aim[b] = own ? acc[3 * NK + tid + 256 * b] : 0.0;
+    }
+    for (long long s0 = s_lo; s0 <= s_hi; s0 += G) {
+        // z = w x + i w y of the round's segments, stored in bit-reversed order
+        for (int e = tid; e < G * L; e += 256) {
+            const int g = e >> LOG2L, j = e & (L - 1);
+            if (s0 + g > s_hi) continue;
+            const long long m = (s0 + g) * A.hop + j;
+            const double vx = m >= A.m0 ? up[(m - A.m0) * C.nu] : cx[m & (L - 1)];
+            const double vy = m >= A.m0 ? yp[(m - A.m0) * A.ny] : cy[m & (L - 1)];
+            const int r = (int)(__brev((unsigned)j) >> (32 - LOG2L));
+            const double wj = A.w[j];
+            sre[g * PITCH + r + (r >> 5)] = wj * vx;
+            sim[g * PITCH + r + (r >> 5)] = wj * vy;
+        }
+        __syncthreads();
+#pragma unroll
+        for (int q = 0; q + 2 <= LOG2L; q += 2) {
+            const int h = 1 << q;
+            for (int e = tid; e < G * Q; e += 256) {
+                const int g = e >> (LOG2L - 2), j = e & (Q - 1), r = j & (h - 1), i0 = ((j >> q) << (q + 2)) + r;
+                if (s0 + g > s_hi) continue;
+                double *re = sre + g * PITCH, *im = sim + g * PITCH;
+                int at[4];
+                double xr[4], xi[4];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    at[c] = i0 + c * h + ((i0 + c * h) >> 5);
+                    xr[c] = re[at[c]];
+                    xi[c] = im[at[c]];
+                }
+                const double *ta = A.tw + 2 * ((long long)r << (LOG2L - 1 - q));
+                const double *tb = A.tw + 2 * ((long long)r << (LOG2L - 2 - q));
+                const double *tc = A.tw + 2 * ((long long)(r + h) << (LOG2L - 2 - q));
+                const double ar = ta[0], ai = ta[1], br = tb[0], bi = tb[1], cr = tc[0], ci = tc[1];
+                acme_meas_spec_bf(xr[0], xi[0], xr[1], xi[1], ar, ai);
+                acme_meas_spec_bf(xr[2], xi[2], xr[3], xi[3], ar, ai);
+                acme_meas_spec_bf(xr[0], xi[0], xr[2], xi[2], br, bi);
+                acme_meas_spec_bf(xr[1], xi[1], xr[3], xi[3], cr, ci);
+#pragma unroll
+                for (int c = 0; c < 4; ++c) {
+                    re[at[c]] = xr[c];
+                    im[at[c]] = xi[c];
+                }
+            }
+            __syncthreads();
+        }
+        if (LOG2L & 1) {                                // the last stage on its own: h = L / 2, twiddle index i
+            for (int e = tid; e < G * (L / 2); e += 256) {
+                const int g = e >> (LOG2L - 1), j = e & (L / 2 - 1);
+                if (s0 + g > s_hi) continue;
+                double *re = sre + g * PITCH, *im = sim + g * PITCH;
+                const int a0 = j + (j >> 5), a1 = j + L / 2 + ((j + L / 2) >> 5);
+                double xr0 = re[a0], xi0 = im[a0], xr1 = re[a1], xi1 = im[a1];
+                acme_meas_spec_bf(xr0, xi0, xr1, xi1, A.tw[2 * j], A.tw[2 * j + 1]);
+                re[a0] = xr0;
+                im[a0] = xi0;
+                re[a1] = xr1;
+                im[a1] = xi1;
+            }
+            __syncthreads();
+        }
+        // X and Y of the round's segments split off Z, and the four products into the bins' chains, in segment order
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+            const int k = tid + 256 * b, n = (L - k) & (L - 1);
+            if (k > L / 2) continue;
+            const int ak = k + (k >> 5), an = n + (n >> 5);
+            for (int g = 0; g < G && s0 + g <= s_hi; ++g) {
+                const double zrk = sre[g * PITCH + ak], zik = sim[g * PITCH + ak];
+                const double zrn = sre[g * PITCH + an], zin = sim[g * PITCH + an];
+                const double xr = 0.5 * (zrk + zrn), xi = 0.5 * (zik - zin);
+                const double yr = 0.5 * (zik + zin), yi = 0.5 * (zrn - zrk);
+                const double p0 = xr * xr, p1 = xi * xi, p2 = yr * yr, p3 = yi * yi;
+                const double p4 = xr * yr, p5 = xi * yi, p6 = xr * yi, p7 = xi * yr;
+                const double sxx = p0 + p1, syy = p2 + p3, sre_ = p4 + p5, sim_ = p6 - p7;
+                axx[b] = axx[b] + sxx;
+                ayy[b] = ayy[b] + syy;
+                are[b] = are[b] + sre_;
+                aim[b] = aim[b] + sim_;
+            }
+        }
+        __syncthreads();                                // (the next round's load overwrites the vectors)
+    }
+    if (s_lo <= s_hi) {
+#pragma unroll
+        for (int b = 0; b < NB; ++b)
+            if (tid + 256 * b <= L / 2) {
+                acc[tid + 256 * b] = axx[b];
+                acc[NK + tid + 256 * b] = ayy[b];
+                acc[2 * NK + tid + 256 * b] = are[b];
+                acc[3 * NK + tid + 256 * b] = aim[b];
+            }
+    }
+    // the chunk's last min(len, L) samples into the rings (every read of them lies before a barrier above)
+    for (long long t = (A.len > L ? A.len - L : 0) + tid; t < A.len; t += 256) {
+        cx[(A.m0 + t) & (L - 1)] = up[t * C.nu];
+        cy[(A.m0 + t) & (L - 1)] = yp[t * A.ny];
+    }
+}
 namespace acme {
+template <int LOG2L>
+inline int meas_cross_launch_l(const MeasCrossArgs &C, hipStream_t st) {
+    if constexpr (LOG2L > 12) {
+        return (int)hipErrorInvalidValue;
+    } else {
+        if ((1ll << LOG2L) != C.S.L) return meas_cross_launch_l<LOG2L + 1>(C, st);
+        hipLaunchKernelGGL(acme_meas_cross_kernel<LOG2L>, dim3((unsigned)(C.S.n * C.S.nrows)), dim3(256), 0, st, C);
+        return (int)hipGetLastError();
+    }
+}
+inline int meas_cross_launch(const MeasCrossArgs &C, hipStream_t st) {
+    return C.S.n * C.S.nrows > 0 ? meas_cross_launch_l<6>(C, st) : 0;
+}
+inline int meas_cross_zero(double *p, size_t count) { return (int)hipMemset(p, 0, sizeof(double) * count); }
 template <int LOG2L>
 inline int meas_spectrum_launch_l(const MeasSpecArgs &A, hipStream_t st) {
     if constexpr (LOG2L > 12) {
@@ -990,6 +1154,66 @@ inline int meas_spectrum_launch(const MeasSpecArgs &A, void *) {
     return 0;
 }
 inline int meas_spectrum_zero(double *p, size_t count) {
+    std::fill(p, p + count, 0.0);
+    return 0;
+}
+// cross-spectrum: the contract's arithmetic literally, pair by pair, segment by segment, stage by stage
+ACME_NO_CONTRACT_FN inline void meas_cross_chain(const MeasCrossArgs &C, long long p) {
+    ACME_NO_CONTRACT
+    const MeasSpecArgs &A = C.S;
+    const long long i = p / A.nrows, L = A.L, NK = L / 2 + 1;
+    const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    const double *up = C.u + (i * C.upitch + A.t0) * C.nu + C.in_row;
+    double *cx = A.carry + p * (2 * L), *cy = cx + L, *acc = A.acc + p * (4 * NK);
+    long long s_lo, s_hi;
+    meas_spec_segments(A.m0, A.len, L, A.hop, &s_lo, &s_hi);
+    int bits = 0;
+    while ((1ll << bits) < L) ++bits;
+    std::vector<double> vr((size_t)L), vi((size_t)L);
+    for (long long s = s_lo; s <= s_hi; ++s) {
+        for (long long j = 0; j < L; ++j) {
+            const long long m = s * A.hop + j;
+            long long r = 0;
+            for (int k = 0; k < bits; ++k) r |= (j >> k & 1) << (bits - 1 - k);
+            vr[(size_t)r] = A.w[j] * (m >= A.m0 ? up[(m - A.m0) * C.nu] : cx[m & (L - 1)]);
+            vi[(size_t)r] = A.w[j] * (m >= A.m0 ? yp[(m - A.m0) * A.ny] : cy[m & (L - 1)]);
+        }
+        for (long long h = 1; h < L; h *= 2)
+            for (long long i0 = 0; i0 < L; ++i0) {
+                if (i0 & h) continue;
+                const long long k = (i0 & (h - 1)) * (L / (2 * h));
+                const double wr = A.tw[2 * k], wi = A.tw[2 * k + 1], br = vr[(size_t)(i0 + h)], bi = vi[(size_t)(i0 + h)];
+                const double p0 = wr * br, p1 = wi * bi, p2 = wr * bi, p3 = wi * br;
+                const double tr = p0 - p1, ti = p2 + p3;
+                vr[(size_t)(i0 + h)] = vr[(size_t)i0] - tr;
+                vi[(size_t)(i0 + h)] = vi[(size_t)i0] - ti;
+                vr[(size_t)i0] = vr[(size_t)i0] + tr;
+                vi[(size_t)i0] = vi[(size_t)i0] + ti;
+            }
+        for (long long k = 0; k <= L / 2; ++k) {
+            const long long n = (L - k) & (L - 1);
+            const double zrk = vr[(size_t)k], zik = vi[(size_t)k], zrn = vr[(size_t)n], zin = vi[(size_t)n];
+            const double xr = 0.5 * (zrk + zrn), xi = 0.5 * (zik - zin);
+            const double yr = 0.5 * (zik + zin), yi = 0.5 * (zrn - zrk);
+            const double q0 = xr * xr, q1 = xi * xi, q2 = yr * yr, q3 = yi * yi;
+            const double q4 = xr * yr, q5 = xi * yi, q6 = xr * yi, q7 = xi * yr;
+            const double sxx = q0 + q1, syy = q2 + q3, sre = q4 + q5, sim = q6 - q7;
+            acc[k] = acc[k] + sxx;
+            acc[NK + k] = acc[NK + k] + syy;
+            acc[2 * NK + k] = acc[2 * NK + k] + sre;
+            acc[3 * NK + k] = acc[3 * NK + k] + sim;
+        }
+    }
+    for (long long t = A.len > L ? A.len - L : 0; t < A.len; ++t) {
+        cx[(A.m0 + t) & (L - 1)] = up[t * C.nu];
+        cy[(A.m0 + t) & (L - 1)] = yp[t * A.ny];
+    }
+}
+inline int meas_cross_launch(const MeasCrossArgs &C, void *) {
+    for (long long p = 0; p < C.S.n * C.S.nrows; ++p) meas_cross_chain(C, p);
+    return 0;
+}
+inline int meas_cross_zero(double *p, size_t count) {
     std::fill(p, p + count, 0.0);
     return 0;
 }

@@ -69,6 +69,8 @@ ABI_SYMBOLS = [
     "acme_batch_set_measurement_fold", "acme_batch_get_measurement_fold", "acme_batch_get_measurement_fold_sums",
     "acme_batch_set_measurement_spectrum", "acme_batch_get_measurement_spectrum", "acme_batch_get_measurement_spectrum_sums",
     "acme_batch_get_measurement_spectrum_table",
+    "acme_batch_set_measurement_cross", "acme_batch_get_measurement_cross", "acme_batch_get_measurement_cross_sums",
+    "acme_batch_get_measurement_cross_table",
 ]
 
 SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE, SOURCE_NOISE = 1, 2, 3, 4, 5
@@ -203,6 +205,10 @@ class Library:
         L.acme_batch_get_measurement_spectrum.argtypes = [vp, dp, lp, lp]
         L.acme_batch_get_measurement_spectrum_sums.argtypes = [vp, dp]
         L.acme_batch_get_measurement_spectrum_table.argtypes = [vp, dp, dp]
+        L.acme_batch_set_measurement_cross.argtypes = [vp, C.c_int, C.c_longlong, C.c_longlong, dp]
+        L.acme_batch_get_measurement_cross.argtypes = [vp, dp, lp, lp]
+        L.acme_batch_get_measurement_cross_sums.argtypes = [vp, dp]
+        L.acme_batch_get_measurement_cross_table.argtypes = [vp, dp, dp]
 
     def check(self, rc):
         if rc < 0:
@@ -422,6 +428,77 @@ class MeasurementSpectrum:
         return cls(np.concatenate([p.power for p in parts]), a.segments, a.count, a.rows, a.window, a.hop)
 
 
+class MeasurementCross:
+    """What ``ModelRunner.measurement_cross()`` returns: the Welch-averaged auto- and cross-spectra of input row ``in_row``
+    (x) and the measured output rows (y).  ``sxx``, ``syy`` (N, nrows, nfft / 2 + 1) real and ``sxy`` complex: the means over
+    ``segments`` segments of |X|^2, |Y|^2 and conj(X) Y with X, Y = FFT(w x), FFT(w y), unscaled (NaN while ``segments`` is 0;
+    ``raw``: the sums); ``count`` the samples measured, ``rows`` the measured output rows, ``window`` the nfft window
+    values, ``hop`` the segments' spacing."""
+
+    def __init__(self, sxx, syy, sxy, segments, count, rows, in_row, window, hop):
+        self.sxx, self.syy, self.sxy = sxx, syy, sxy
+        self.segments, self.count, self.rows, self.in_row = int(segments), int(count), tuple(rows), int(in_row)
+        self.window, self.hop = np.asarray(window, dtype=np.float64), int(hop)
+
+    @property
+    def nfft(self):
+        return len(self.window)
+
+    def freqs(self, fs):
+        """the bins' frequencies, k fs / nfft"""
+        return np.arange(self.nfft // 2 + 1) * (float(fs) / self.nfft)
+
+    def transfer(self, estimator="h1"):
+        """the frequency response from x to y: "h1", ``sxy / sxx`` (unbiased under noise on the output), or "h2",
+        ``syy / conj(sxy)`` (under noise on the input) -- complex (N, nrows, nfft / 2 + 1)"""
+        if estimator == "h1":
+            return self.sxy / self.sxx
+        if estimator == "h2":
+            return self.syy / np.conj(self.sxy)
+        raise ValueError(f"estimator {estimator!r}: \"h1\" or \"h2\"")
+
+    def coherence(self):
+        """the magnitude-squared coherence ``|sxy|^2 / (sxx syy)``: 1 where y depends linearly on x alone"""
+        return (self.sxy.real ** 2 + self.sxy.imag ** 2) / (self.sxx * self.syy)
+
+    def _psd(self, power, fs):
+        d = power / (float(fs) * np.sum(self.window ** 2))
+        d[..., 1:-1] *= 2.0
+        return d
+
+    def input_psd(self, fs):
+        """the one-sided power spectral density of x, scaled as ``MeasurementSpectrum.psd``"""
+        return self._psd(self.sxx, fs)
+
+    def output_psd(self, fs):
+        """the one-sided power spectral density of y, scaled as ``MeasurementSpectrum.psd``"""
+        return self._psd(self.syy, fs)
+
+    @classmethod
+    def concatenate(cls, parts):
+        a = parts[0]
+        if any((p.segments, p.count, p.rows, p.in_row, p.hop) != (a.segments, a.count, a.rows, a.in_row, a.hop)
+               or not np.array_equal(p.window, a.window) for p in parts):
+            raise ValueError("the shards' cross-spectra differ in their segments, sample counts, rows or windows")
+        return cls(*(np.concatenate([getattr(p, n) for p in parts]) for n in ("sxx", "syy", "sxy")), a.segments, a.count, a.rows,
+                   a.in_row, a.window, a.hop)
+
+
+def segment_window(nfft, window):
+    """the ``window`` argument of ``set_measurement_spectrum`` / ``set_measurement_cross`` as the ABI takes it: "hann" (periodic),
+    "rect" (None: all ones) or ``nfft`` values"""
+    if isinstance(window, str):
+        if window == "hann":
+            return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(max(nfft, 0)) / max(nfft, 1))
+        if window == "rect":
+            return None
+        raise ValueError(f"window {window!r}: \"hann\", \"rect\" or an array of nfft values")
+    w = np.ascontiguousarray(window, dtype=np.float64)
+    if w.shape != (nfft,):
+        raise DimensionMismatch(f"the window needs {nfft} values")
+    return w
+
+
 def measure_spec(ny, start=0, length=0, f0=None, harmonics=0, rows=None):
     """((start, length, f_num, f_den, harmonics, row mask), measured rows) -- acme_batch_set_measurement's arguments -- from
     ``ModelRunner.set_measurement``'s: ``f0`` a Fraction of fs or
@@ -541,6 +618,7 @@ class ModelRunner:
         self._series = (0, None)        # (the armed start, (win, hop, windows) of a series or None)
         self._fold = False              # a fold is set on the armed measurement
         self._spectrum = None           # (nfft, hop) of the spectrum set on the armed measurement
+        self._cross = None              # (nfft, hop, in_row) of the cross-spectrum set on the armed measurement
         self._sources = {}              # input row -> kind, while the row has a source
         self._sine = {}                 # input row -> (f_den, f_num as armed) of its sine source
         self._progress_cb = None
@@ -633,6 +711,7 @@ class ModelRunner:
         self._series = (int(start), None)
         self._fold = False
         self._spectrum = None
+        self._cross = None
         return self
 
     def set_measurement_bins(self, coef, start=0, length=0, rows=None, f_den=None, f_num=None, tones_from_source=None):
@@ -669,6 +748,7 @@ class ModelRunner:
         self._series = (int(start), None)
         self._fold = False
         self._spectrum = None
+        self._cross = None
         return self
 
     def measurement_plan(self):
@@ -691,6 +771,7 @@ class ModelRunner:
         self._series = (0, None)
         self._fold = False
         self._spectrum = None
+        self._cross = None
         return self
 
     def set_measurement_series(self, win, hop=None, windows=1):
@@ -776,17 +857,7 @@ class ModelRunner:
             raise AcmeError("no measurement is armed")
         nfft = int(nfft)
         hop = nfft // 2 if hop is None else int(hop)
-        if isinstance(window, str):
-            if window == "hann":
-                w = 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(max(nfft, 0)) / max(nfft, 1))
-            elif window == "rect":
-                w = None
-            else:
-                raise ValueError(f"window {window!r}: \"hann\", \"rect\" or an array of nfft values")
-        else:
-            w = np.ascontiguousarray(window, dtype=np.float64)
-            if w.shape != (nfft,):
-                raise DimensionMismatch(f"the window needs {nfft} values")
+        w = segment_window(nfft, window)
         self.lib.check(self.lib.L.acme_batch_set_measurement_spectrum(self.h, nfft, hop, None if w is None else _dp(w)))
         self._spectrum = (nfft, hop)
         return self
@@ -814,6 +885,50 @@ class ModelRunner:
         if raw:
             self.lib.check(self.lib.L.acme_batch_get_measurement_spectrum_sums(self.h, _dp(out)))
         return MeasurementSpectrum(out, seg.value, count.value, rows, self.measurement_spectrum_table()[0], hop)
+
+    def set_measurement_cross(self, in_row, nfft, hop=None, window="hann"):
+        """The cross-spectrum of input row ``in_row`` and the measured output rows over the armed measurement's window
+        (``acme_batch_set_measurement_cross``): segments of ``nfft`` samples (a power of two, 64 ... 4096), one every ``hop``
+        (None: ``nfft // 2``), each multiplied by ``window`` -- "hann" (periodic), "rect" or ``nfft`` values --; the input
+        row, as the run sees it at the base rate (the caller's u, a constant row or a source), and a measured row go
+        through one complex transform on the device, and |X|^2, |Y|^2 and conj(X) Y are accumulated per instance, measured
+        row and bin.  Needs an armed measurement (any form, any window) that has not been fed yet; not together with a
+        series; ``measurement_cross`` reads it."""
+        if self._meas is None:
+            raise AcmeError("no measurement is armed")
+        nfft = int(nfft)
+        hop = nfft // 2 if hop is None else int(hop)
+        w = segment_window(nfft, window)
+        self.lib.check(self.lib.L.acme_batch_set_measurement_cross(self.h, int(in_row), nfft, hop, None if w is None else _dp(w)))
+        self._cross = (nfft, hop, int(in_row))
+        return self
+
+    def measurement_cross_table(self):
+        """(w (nfft,), tw (nfft / 2, 2)): the window and the twiddles (cos, -sin)(2 pi k / nfft) the kernel uses
+        (``acme_batch_get_measurement_cross_table``)"""
+        if self._meas is None or self._cross is None:
+            raise AcmeError("no measurement cross-spectrum is set")
+        nfft = self._cross[0]
+        w, tw = np.empty(nfft), np.empty((nfft // 2, 2))
+        self.lib.check(self.lib.L.acme_batch_get_measurement_cross_table(self.h, _dp(w), _dp(tw)))
+        return w, tw
+
+    def measurement_cross(self, raw=False):
+        """the cross-spectrum so far (``acme_batch_get_measurement_cross``): a ``MeasurementCross``.  ``raw``: it holds the
+        bins' sums, undivided (``acme_batch_get_measurement_cross_sums``; the tests pin the chains on them)."""
+        if self._meas is None or self._cross is None:
+            raise AcmeError("no measurement cross-spectrum is set")
+        nfft, hop, in_row = self._cross
+        rows = self._meas[1]
+        seg, count = C.c_longlong(0), C.c_longlong(0)
+        out = np.empty((self.n, len(rows), 4, nfft // 2 + 1))
+        self.lib.check(self.lib.L.acme_batch_get_measurement_cross(self.h, None if raw else _dp(out), C.byref(seg), C.byref(count)))
+        if raw:
+            self.lib.check(self.lib.L.acme_batch_get_measurement_cross_sums(self.h, _dp(out)))
+        sxy = np.empty(out[:, :, 2].shape, dtype=np.complex128)     # (the planes' bits: no arithmetic touches them)
+        sxy.real, sxy.imag = out[:, :, 2], out[:, :, 3]
+        return MeasurementCross(out[:, :, 0].copy(), out[:, :, 1].copy(), sxy, seg.value, count.value, rows, in_row,
+                                self.measurement_cross_table()[0], hop)
 
     def reset_measurement(self):
         """zero the accumulators and restart the window's clock (``acme_batch_reset_measurement``)"""
@@ -1478,6 +1593,17 @@ class MultiDeviceRunner:
     def measurement_spectrum(self, raw=False):
         """the shards' ``MeasurementSpectrum`` results, concatenated along the instances (``raw`` as ``ModelRunner``'s)"""
         return MeasurementSpectrum.concatenate([r.measurement_spectrum(raw) for r in self.runners if r is not None])
+
+    def set_measurement_cross(self, in_row, nfft, hop=None, window="hann"):
+        """``ModelRunner.set_measurement_cross`` on every device's batch"""
+        for r in self.runners:
+            if r is not None:
+                r.set_measurement_cross(in_row, nfft, hop, window)
+        return self
+
+    def measurement_cross(self, raw=False):
+        """the shards' ``MeasurementCross`` results, concatenated along the instances (``raw`` as ``ModelRunner``'s)"""
+        return MeasurementCross.concatenate([r.measurement_cross(raw) for r in self.runners if r is not None])
 
     def measure(self, u=None, check=True, T=None):
         """``run`` with y = NULL on every device (``u``: (N, T, nu), the ABI's layout); only the measurements are fed.

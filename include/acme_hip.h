@@ -413,6 +413,53 @@ int acme_batch_get_measurement_spectrum(acme_batch *b, double *out, long long *s
 int acme_batch_get_measurement_spectrum_sums(acme_batch *b, double *out);
 /* the window w[L] and the table tw[L / 2][2] the kernel uses (either may be NULL) */
 int acme_batch_get_measurement_spectrum_table(acme_batch *b, double *w, double *tw);
+/* A CROSS-SPECTRUM of the window: the armed measurement (any of the three forms, no sample fed since arming or the last reset)
+ * also relates ONE input row to every measured output row over the spectrum's segments -- Sxx, Syy and the complex Sxy per
+ * instance, measured row and bin k = 0 ... L / 2: system identification from one broadband run, the H1 estimate of the
+ * frequency response Sxy / Sxx and the coherence |Sxy|^2 / (Sxx Syy) per instance, N x nrows x 4 x (L / 2 + 1) doubles in place
+ * of u [N][T][nu] and y [N][T][ny].
+ *   in_row  an input row of the model, 0 <= in_row < nu.  x is that row's base-rate sample as the run sees it: the caller's u,
+ *           a constant row of acme_batch_run_const, or a source of any kind (CONST included).
+ *   L, hop, w   as acme_batch_set_measurement_spectrum's; the segments and their count are the spectrum's too
+ *           (segments = count >= L ? (count - L) / hop + 1 : 0).
+ * y is a measured output row.  Under oversampling both are the BASE-RATE signals, u before the interpolation and y after the
+ * decimation: the estimate then includes the resampler's response.
+ * Arithmetic, per segment and pair (instance i, measured row r) -- every operation rounded on its own, NO fused multiply-add:
+ *   1. a_j = w[j] x[s hop + j], b_j = w[j] y[s hop + j], one product each.
+ *   2. Z = FFT_L(a + i b), the spectrum's radix-2 decimation-in-time transform of the COMPLEX vector: its table, the
+ *      bit-reversed load of both parts, its stage order and its butterfly (tr = wr br - wi bi, ti = wr bi + wi br, a + t,
+ *      a - t); nothing is assumed zero.
+ *   3. for k = 0 ... L / 2, with n = (L - k) mod L:
+ *        Xr = 0.5 (Zr_k + Zr_n)   Xi = 0.5 (Zi_k - Zi_n)   Yr = 0.5 (Zi_k + Zi_n)   Yi = 0.5 (Zr_n - Zr_k)
+ *   4. four chains per bin, each from 0.0 in segment order:
+ *        xx += (Xr Xr + Xi Xi)   yy += (Yr Yr + Yi Yi)   re += (Xr Yr + Xi Yi)   im += (Xr Yi - Xi Yr)
+ *      so that Sxy = re + i im = sum conj(X) Y and H1 = Sxy / Sxx.
+ * As for the spectrum this fixes the VALUES, not the data flow.  PACKING: the two signals share one transform, so the rounding
+ * errors of the larger enter the bins of the smaller: X and Y are each within sqrt(L) ||z||_2 (q eta / (1 - q eta) + u) (plus
+ * the split's one addition) of the exact transform, with ||z||_2^2 = ||a||_2^2 + ||b||_2^2, q = log2 L and eta of DESIGN.md
+ * 2.5j -- relative to ||z||, not to the signal's own norm: with |y| = 1000 |x| the X bins are off by some 10^-13 of their
+ * largest, not 10^-16.  For that reason xx is kept per PAIR, not per instance: it is the xx of that pair's transform.
+ * out planes in order xx, yy, re, im; no scaling by the sample rate or the window's power is applied.
+ * The sums depend on nothing but the run's samples, as the spectrum's: chunk, slice and call boundaries, memory kinds, entry
+ * points, y stored or NULL, the oversampling factor and ACME_OS_SLICE change none of their bits.  The measurement's own
+ * accumulators and launches are what they are without it; it takes one more kernel per chunk of the window and, per pair,
+ * 2 L + 4 (L / 2 + 1) doubles of device memory (a ring of the last L samples of x and one of y, and the four planes).  A fold,
+ * a spectrum and a cross-spectrum may all be set together.  The cost per sample grows as the spectrum's: keep hop >= L / 8 on
+ * wide batches.
+ * ACME_ERR_INVALID: no measurement armed, samples already fed, L not a power of two or out of range, hop out of range, a
+ * non-finite window value, in_row out of range, a model without inputs (nu == 0).  ACME_ERR_UNSUPPORTED together with a series,
+ * whichever is set first.  Setting it again replaces the earlier one.  _reset_measurement zeroes the sums and the rings and keeps
+ * L, hop, w, the table and in_row; arming any form or _clear_measurement removes it; acme_batch_set_matrices carries it with
+ * the accumulators.  A batch without a cross-spectrum launches and allocates what it always did. */
+int acme_batch_set_measurement_cross(acme_batch *b, int in_row, long long L, long long hop, const double *w /* host [L], NULL: all 1.0 */);
+/* the cross-spectrum so far: out[N][nrows][4][L / 2 + 1] (may be NULL) = sums / segments, NaN everywhere while segments == 0;
+ * *segments, *count: complete segments and samples measured (may be NULL).  ACME_ERR_INVALID without a cross-spectrum.  Joins a
+ * pending acme_batch_run_async and synchronises the device. */
+int acme_batch_get_measurement_cross(acme_batch *b, double *out, long long *segments, long long *count);
+/* the same planes undivided: out[N][nrows][4][L / 2 + 1] (not NULL), the chains' sums themselves (NaN while segments == 0) */
+int acme_batch_get_measurement_cross_sums(acme_batch *b, double *out);
+/* the window w[L] and the table tw[L / 2][2] the kernel uses (either may be NULL) */
+int acme_batch_get_measurement_cross_table(acme_batch *b, double *w, double *tw);
 /* switch the measurement off (y = NULL is refused again) */
 int acme_batch_clear_measurement(acme_batch *b);
 /* zero the accumulators and restart the window's clock (the armed parameters stay) */

@@ -38,7 +38,8 @@ export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host
        MeasureSpec, Measurement, set_measurement!, clear_measurement!, reset_measurement!, measurement, measurement_plan, measure!,
        set_source!, clear_source!, source_clock, source_clock!, run_sources!, render_sources,
        set_source_multisine!, set_source_noise!, set_measurement_bins!, set_measurement_series!, measurement_series,
-       set_measurement_fold!, measurement_fold, set_measurement_spectrum!, measurement_spectrum
+       set_measurement_fold!, measurement_fold, set_measurement_spectrum!, measurement_spectrum,
+       set_measurement_cross!, measurement_cross
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
 
@@ -221,6 +222,7 @@ mutable struct BatchRunner
     meas::Any                         # the armed MeasureSpec (nothing: none)
     sources::Set{Int}                 # the input rows (1-based) that have a source
     spectrum::Int                     # nfft of the spectrum set on the armed measurement (0: none)
+    cross::Int                        # nfft of the cross-spectrum set on the armed measurement (0: none)
 end
 
 # @showprogress of run!(runner, y, u) (src/ACME.jl:587-604,653): the library reports after every time slice of a
@@ -239,7 +241,7 @@ function BatchRunner(model::DiscreteModel, n::Integer; device::Integer=-1,
     b = Ref{Ptr{Cvoid}}()
     check(ccall((:acme_batch_create, lib), Cint, (Ptr{Cvoid}, Clonglong, Ref{AcmeOptions}, Ref{Ptr{Cvoid}}),
                 mh.h, n, opts, b))
-    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress, nothing, Set{Int}(), 0)
+    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress, nothing, Set{Int}(), 0, 0)
     finalizer(r -> ccall((:acme_batch_destroy, lib), Cvoid, (Ptr{Cvoid},), r.h), r)
     if showprogress
         cb = @cfunction(progress_trampoline, Cvoid, (Ptr{Cvoid}, Clonglong, Clonglong))
@@ -482,6 +484,7 @@ function set_measurement!(r::BatchRunner, spec::MeasureSpec)
                 r.h, spec.start, spec.length, spec.f_num, spec.f_den, spec.harmonics, spec.rows))
     r.meas = spec
     r.spectrum = 0
+    r.cross = 0
     return r
 end
 function set_measurement!(r::BatchRunner; f_den=nothing, f_num=nothing, kwargs...)
@@ -505,6 +508,7 @@ function set_measurement!(r::BatchRunner, spec::MeasureSpec, f_den::Int64, f_num
                 r.h, spec.start, spec.length, f_den, f_num, spec.harmonics, spec.rows))
     r.meas = spec
     r.spectrum = 0
+    r.cross = 0
     return r
 end
 
@@ -529,6 +533,7 @@ function set_measurement_bins!(r::BatchRunner, coef::Matrix{<:Integer}, f_den::I
                 r.h, spec.start, spec.length, f_den, tones, f_num, bins, c, spec.rows))
     r.meas = spec
     r.spectrum = 0
+    r.cross = 0
     return r
 end
 
@@ -555,6 +560,7 @@ function clear_measurement!(r::BatchRunner)
     check(ccall((:acme_batch_clear_measurement, lib), Cint, (Ptr{Cvoid},), r.h))
     r.meas = nothing
     r.spectrum = 0
+    r.cross = 0
     return r
 end
 
@@ -696,6 +702,54 @@ function measurement_spectrum(r::BatchRunner; sums::Bool=false)
     window, table = Vector{Float64}(undef, nfft), Matrix{Float64}(undef, 2, nfft ÷ 2)
     check(ccall((:acme_batch_get_measurement_spectrum_table, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), r.h, window, table))
     return (power=power, segments=segments[], count=count[], window=window, table=table)
+end
+
+"""
+    set_measurement_cross!(runner, in_row, nfft; hop=nfft ÷ 2, window=nothing)
+
+The cross-spectrum of input row `in_row` (1-based) and the measured output rows over the armed measurement's window
+(`acme_batch_set_measurement_cross`): segments of `nfft` samples (a power of two, 64 ... 4096), one every `hop`, each multiplied
+by `window::Vector{Float64}` (`nothing`: the periodic Hann window; `:rect`: all ones); the input row as the run sees it at the
+base rate and a measured row go through one complex transform on the device, and |X|^2, |Y|^2 and conj(X) Y are accumulated
+per instance, measured row and bin.  Needs an armed measurement that has not been fed yet; not together with a series.
+"""
+function set_measurement_cross!(r::BatchRunner, in_row::Integer, nfft::Integer; hop::Integer=nfft ÷ 2, window=nothing)
+    r.meas === nothing && error("no measurement is armed")
+    w = window === :rect ? Float64[] :
+        window === nothing ? [0.5 - 0.5 * cos(2pi * j / nfft) for j in 0:nfft-1] : convert(Vector{Float64}, window)
+    window === :rect || length(w) == nfft || throw(DimensionMismatch("the window needs $nfft values"))
+    GC.@preserve w check(ccall((:acme_batch_set_measurement_cross, lib), Cint,
+                (Ptr{Cvoid}, Cint, Clonglong, Clonglong, Ptr{Cdouble}), r.h, in_row - 1, nfft, hop, ptr_or_null(w)))
+    r.cross = Int(nfft)
+    return r
+end
+
+"""
+    measurement_cross(runner; sums=false) -> (sxx, syy, sxy, segments, count, window, table)
+
+The cross-spectrum so far (`acme_batch_get_measurement_cross`): `sxx`, `syy` (real) and `sxy` (complex) are
+(nfft ÷ 2 + 1) x nrows x N, the means over `segments` segments of |X|^2, |Y|^2 and conj(X) Y, unscaled (NaN while
+`segments == 0`); `sums=true`: the bins' sums, undivided (`acme_batch_get_measurement_cross_sums`).  The H1 estimate of the
+frequency response is `sxy ./ sxx`, the coherence `abs2.(sxy) ./ (sxx .* syy)`.  `window` (nfft) and `table` (2 x nfft ÷ 2) are
+what the kernel uses (`acme_batch_get_measurement_cross_table`).
+"""
+function measurement_cross(r::BatchRunner; sums::Bool=false)
+    spec = r.meas
+    (spec === nothing || r.cross == 0) && error("no measurement cross-spectrum is set")
+    ny = ACME.ny(r.model)
+    nrows = spec.rows == 0 ? min(ny, 64) : count_ones(spec.rows)
+    nfft = r.cross
+    segments, count = Ref{Clonglong}(0), Ref{Clonglong}(0)
+    out = Array{Float64,4}(undef, nfft ÷ 2 + 1, 4, nrows, r.n)       # the ABI's [N][nrows][4][nfft / 2 + 1]
+    check(ccall((:acme_batch_get_measurement_cross, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Clonglong}, Ptr{Clonglong}),
+                r.h, out, segments, count))
+    if sums
+        check(ccall((:acme_batch_get_measurement_cross_sums, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), r.h, out))
+    end
+    window, table = Vector{Float64}(undef, nfft), Matrix{Float64}(undef, 2, nfft ÷ 2)
+    check(ccall((:acme_batch_get_measurement_cross_table, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), r.h, window, table))
+    return (sxx=out[:, 1, :, :], syy=out[:, 2, :, :], sxy=complex.(out[:, 3, :, :], out[:, 4, :, :]),
+            segments=segments[], count=count[], window=window, table=table)
 end
 
 """
