@@ -184,6 +184,14 @@ struct acme_batch {
         double *d_cross_w = nullptr, *d_cross_tw = nullptr;
         double *d_cross_acc = nullptr;           // [N nrows][4][L / 2 + 1] sums of |X|^2, |Y|^2, Re and Im conj(X) Y, from 0.0
         double *d_cross_carry = nullptr;         // [N nrows][2][L]: the most recent samples of x and of y, sample m at m mod L
+        // target (acme_batch_set_measurement_target): the residual against a looped waveform of the caller's
+        bool target = false;
+        long long tgt_K = 0, tgt_P = 0;
+        double tgt_c = 0.0;                      // the pre-emphasis coefficient
+        double *d_tgt = nullptr;                 // [K][nrows][P]
+        int *d_tgt_which = nullptr, *d_tgt_wuni = nullptr;      // [N], [(N nrows + 63) / 64]: the plan (meas_target_plan)
+        long long *d_tgt_lag = nullptr;          // [N]
+        double *d_tgt_acc = nullptr;             // [9][N nrows]: the seven chains and the carries e_prev, t_prev, from 0.0
     } meas;
     // Input rows generated on the device (acme_batch_set_source_*, acme_source.h): the rows' descriptions and per-instance
     // parameters in device memory, the source clock
@@ -798,6 +806,7 @@ static void meas_release(acme_batch::Measurement &M) {
     (void)be::dfree(M.d_fold_per); (void)be::dfree(M.d_fold);
     (void)be::dfree(M.d_spec_w); (void)be::dfree(M.d_spec_tw); (void)be::dfree(M.d_spec_acc); (void)be::dfree(M.d_spec_carry);
     (void)be::dfree(M.d_cross_w); (void)be::dfree(M.d_cross_tw); (void)be::dfree(M.d_cross_acc); (void)be::dfree(M.d_cross_carry);
+    (void)be::dfree(M.d_tgt); (void)be::dfree(M.d_tgt_which); (void)be::dfree(M.d_tgt_wuni); (void)be::dfree(M.d_tgt_lag); (void)be::dfree(M.d_tgt_acc);
     M = acme_batch::Measurement{};
 }
 
@@ -1495,6 +1504,12 @@ static int meas_step(acme_batch *b, const double *y, long long n, long long pitc
             memcpy(G.S.row, M.row, sizeof(G.S.row));
             HIPCHK(meas_cross_launch(G, st));
         }
+        if (M.target) { // ... and the residual against the target on the same chunk
+            MeasTargetArgs G{y, M.d_tgt_acc, M.d_tgt, M.d_tgt_which, M.d_tgt_lag, M.d_tgt_wuni, b->N, len, pitch, s - M.pos, s - M.start,
+                             M.tgt_P, M.tgt_c, A.ny, M.nrows, {}};
+            memcpy(G.row, M.row, sizeof(G.row));
+            HIPCHK(meas_target_launch(G, st));
+        }
     }
     M.pos += n;
     return ACME_OK;
@@ -2166,6 +2181,10 @@ static int meas_zero(acme_batch *b) {
         HIPCHK(meas_cross_zero(M.d_cross_carry, P * 2 * (size_t)M.cross_L));
         HIPCHK(be::device_sync());
     }
+    if (M.target) {     // the chains and the two carries (the table, which, lag and c stay)
+        HIPCHK(meas_target_zero(M.d_tgt_acc, P * (size_t)MEAS_TARGET_SLOTS));
+        HIPCHK(be::device_sync());
+    }
     M.pos = 0;
     return ACME_OK;
 }
@@ -2338,6 +2357,7 @@ int acme_batch_set_measurement_series(acme_batch *b, long long win, long long ho
     if (M.fold) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a fold (a fold per window is not supported)");
     if (M.spec) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a spectrum (a spectrum per window is not supported)");
     if (M.cross) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a cross-spectrum (a cross-spectrum per window is not supported)");
+    if (M.target) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a target (a target per window is not supported)");
     if (M.length != 0) return fail(ACME_ERR_INVALID, "measurement series: the armed measurement's length must be 0 (the series sets the windows)");
     if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement series: samples have been fed since arming (arm or reset the measurement first)");
     if (win < 1) return fail(ACME_ERR_INVALID, "measurement series: win must be >= 1");
@@ -2637,6 +2657,79 @@ int acme_batch_get_measurement_cross_table(acme_batch *b, double *w, double *tw)
     if (!M.on || !M.cross) return fail(ACME_ERR_INVALID, "no measurement cross-spectrum is set");
     if (w) memcpy(w, M.cross_w.data(), sizeof(double) * M.cross_w.size());
     if (tw) memcpy(tw, M.cross_tw.data(), sizeof(double) * M.cross_tw.size());
+    return ACME_OK;
+}
+
+int acme_batch_set_measurement_target(acme_batch *b, const double *t, long long K, long long P, const int *which, long long *lag,
+                                      double preemph) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    acme_batch::Measurement &M = b->meas;
+    if (!M.on) return fail(ACME_ERR_INVALID, "measurement target: no measurement is armed");
+    if (M.W) return fail(ACME_ERR_UNSUPPORTED, "measurement target: the measurement has a series of windows (a target per window is not supported)");
+    if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement target: samples have been fed since arming (arm or reset the measurement first)");
+    if (!t) return fail(ACME_ERR_INVALID, "measurement target: t is null");
+    if (K < 1 || K > MEAS_MAX_TARGETS) return fail(ACME_ERR_INVALID, "measurement target: K is outside 1 ... " + std::to_string(MEAS_MAX_TARGETS));
+    if (P < 1) return fail(ACME_ERR_INVALID, "measurement target: P must be >= 1");
+    const long long per = K * (long long)(M.nrows > 0 ? M.nrows : 1);       // (<= 64 x 64)
+    if (P > (long long)ACME_MAX_SOURCE_TABLE / per)
+        return fail(ACME_ERR_INVALID, "measurement target: K nrows P exceeds " + std::to_string((long long)ACME_MAX_SOURCE_TABLE));
+    if (!(preemph >= 0.0 && preemph < 1.0)) return fail(ACME_ERR_INVALID, "measurement target: preemph is outside 0 <= c < 1");
+    const size_t total = (size_t)K * (size_t)M.nrows * (size_t)P, N = (size_t)b->N, pairs = N * (size_t)M.nrows;
+    for (size_t k = 0; k < total; ++k)
+        if (!std::isfinite(t[k])) return fail(ACME_ERR_INVALID, "measurement target: t[" + std::to_string(k) + "] is not finite");
+    std::vector<int> wh(N, 0), wuni;
+    std::vector<long long> lg(N, 0);
+    for (size_t i = 0; i < N; ++i) {
+        if (which) wh[i] = which[i];
+        if (lag) lg[i] = lag[i];
+        if (wh[i] < 0 || wh[i] >= K)
+            return fail(ACME_ERR_INVALID, "measurement target: which of instance " + std::to_string(i) + " is outside 0 ... K - 1 = " + std::to_string(K - 1));
+        if (lg[i] < 0 || lg[i] >= P)
+            return fail(ACME_ERR_INVALID, "measurement target: lag of instance " + std::to_string(i) + " is outside 0 ... P - 1 = " + std::to_string(P - 1));
+    }
+    meas_target_plan(wh.data(), lg.data(), b->N, M.nrows, &wuni);
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    (void)be::dfree(M.d_tgt); (void)be::dfree(M.d_tgt_which); (void)be::dfree(M.d_tgt_wuni); (void)be::dfree(M.d_tgt_lag); (void)be::dfree(M.d_tgt_acc);
+    M.d_tgt = M.d_tgt_acc = nullptr;    // (a target set again replaces the earlier one)
+    M.d_tgt_which = M.d_tgt_wuni = nullptr;
+    M.d_tgt_lag = nullptr;
+    M.target = false;
+    HIPCHK(be::dmalloc((void **)&M.d_tgt, sizeof(double) * std::max<size_t>(total, 1)));
+    HIPCHK(be::dmalloc((void **)&M.d_tgt_which, sizeof(int) * std::max<size_t>(N, 1)));
+    HIPCHK(be::dmalloc((void **)&M.d_tgt_lag, sizeof(long long) * std::max<size_t>(N, 1)));
+    HIPCHK(be::dmalloc((void **)&M.d_tgt_wuni, sizeof(int) * std::max<size_t>(wuni.size(), 1)));
+    HIPCHK(be::dmalloc((void **)&M.d_tgt_acc, sizeof(double) * std::max<size_t>(pairs * MEAS_TARGET_SLOTS, 1)));
+    if (total) HIPCHK(be::copy_h2d(M.d_tgt, t, sizeof(double) * total));
+    if (N) HIPCHK(be::copy_h2d(M.d_tgt_which, wh.data(), sizeof(int) * N));
+    if (N) HIPCHK(be::copy_h2d(M.d_tgt_lag, lg.data(), sizeof(long long) * N));
+    if (!wuni.empty()) HIPCHK(be::copy_h2d(M.d_tgt_wuni, wuni.data(), sizeof(int) * wuni.size()));
+    HIPCHK(meas_target_zero(M.d_tgt_acc, pairs * MEAS_TARGET_SLOTS));
+    HIPCHK(be::device_sync());
+    M.tgt_K = K;
+    M.tgt_P = P;
+    M.tgt_c = preemph;
+    M.target = true;
+    return ACME_OK;
+}
+
+int acme_batch_get_measurement_target(acme_batch *b, double *out, long long *count) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const acme_batch::Measurement &M = b->meas;
+    if (!M.on || !M.target) return fail(ACME_ERR_INVALID, "no measurement target is set");
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    const long long end = M.length ? M.start + M.length : LLONG_MAX;
+    const long long cnt = (M.pos < end ? M.pos : end) - M.start;
+    if (count) *count = cnt > 0 ? cnt : 0;
+    if (!out) return ACME_OK;
+    const size_t pairs = (size_t)b->N * M.nrows;
+    std::vector<double> a(pairs * MEAS_TARGET_SLOTS);
+    if (!a.empty()) HIPCHK(be::copy_d2h(a.data(), M.d_tgt_acc, sizeof(double) * a.size()));
+    for (size_t p = 0; p < pairs; ++p)
+        for (int k = 0; k < 7; ++k) out[p * 7 + k] = a[(size_t)k * pairs + p];
     return ACME_OK;
 }
 

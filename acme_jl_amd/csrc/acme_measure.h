@@ -80,6 +80,13 @@
 // shared by an instance's rows would be rewritten by one row's block while another still reads it).  One more kernel per
 // chunk (acme_meas_cross_kernel<log2 L>), the spectrum kernel's shape; the emulator walks meas_cross_chain.
 //
+// TARGET (acme_batch_set_measurement_target): the residual against a looped waveform of the caller's, t = tgt[which_i][j][(m +
+// lag_i) mod P] -- seven chains per pair from 0.0, no fused multiply-add: See += (y - t)^2, Stt += t^2, Syt += y t, St += t,
+// emax = max |y - t|, and behind the pre-emphasis 1 - c z^-1 Pee, Ptt; the two carries e_prev, t_prev live beside them.  The
+// accumulators are [9][N nrows].  One more kernel per chunk (acme_meas_target_kernel): the moments unit's tiles, the chains
+// of a pair split over three waves, a wave whose pairs share (which, row, lag) -- decided on the host at arming,
+// meas_target_plan -- broadcasting its target tile, any other gathering per lane; the emulator walks meas_target_chain.
+//
 // The per-element functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with g++).
 #pragma once
@@ -281,6 +288,77 @@ ACME_HD inline double meas_max(double m, double v) { return (v > m || v != v) ? 
 
 // the accumulators' start values: sum, sq 0; min +inf; max -inf; C_h, S_h 0
 inline double meas_init(int a) { return a == 2 ? INFINITY : a == 3 ? -INFINITY : 0.0; }
+
+// target: the chunk's first sample is number m0 >= 0 of the window (n - start).  acc is [MEAS_TARGET_SLOTS][n * nrows], the
+// planes See, Stt, Syt, St, emax, Pee, Ptt and the two carries e_prev, t_prev, all from 0.0
+constexpr int MEAS_MAX_TARGETS = 64;
+constexpr int MEAS_TARGET_SLOTS = 9;
+constexpr int MEAS_TARGET_WAVES = 3;        // the chains of a pair split over the waves of a block (acme_meas_target_kernel)
+
+struct MeasTargetArgs {
+    const double *y;            // instance i, sample t, row r at y[(i * pitch + t0 + t) * ny + r]
+    double *acc;                // [MEAS_TARGET_SLOTS][n * nrows]
+    const double *tgt;          // [K][nrows][P]
+    const int *which;           // [n]: 0 <= which[i] < K
+    const long long *lag;       // [n]: 0 <= lag[i] < P
+    const int *wuni;            // [(n * nrows + 63) / 64]: != 0 -- the wave's pairs share (which, row, lag)
+    long long n, len, pitch, t0, m0, P;
+    double c;                   // the pre-emphasis coefficient
+    int ny, nrows;
+    unsigned char row[64];      // the measured rows, ascending
+};
+
+// one pair over the chunk, sample after sample: the contract of include/acme_hip.h as a plain loop (the reference order every
+// backend keeps; every product and every sum rounded on its own)
+ACME_HD ACME_NO_CONTRACT_FN inline void meas_target_chain(const MeasTargetArgs &A, long long p) {
+    ACME_NO_CONTRACT
+    const long long Pn = A.n * A.nrows, i = p / A.nrows, j = p - i * A.nrows;
+    const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[j];
+    const double *tg = A.tgt + ((long long)A.which[i] * A.nrows + j) * A.P;
+    double *a = A.acc + p;
+    double see = 0.0, stt = 0.0, syt = 0.0, st = 0.0, emax = 0.0, pee = 0.0, ptt = 0.0, ep = 0.0, tp = 0.0;
+    if (A.m0 != 0) {            // (the window's first sample starts from 0.0 without reading)
+        see = a[0]; stt = a[Pn]; syt = a[2 * Pn]; st = a[3 * Pn]; emax = a[4 * Pn]; pee = a[5 * Pn]; ptt = a[6 * Pn];
+        ep = a[7 * Pn]; tp = a[8 * Pn];
+    }
+    long long s = (A.m0 % A.P + A.lag[i]) % A.P;
+    for (long long k = 0; k < A.len; ++k) {
+        const double y = yp[k * A.ny], t = tg[s];
+        if (++s == A.P) s = 0;
+        const double e = y - t;
+        const double ee = e * e, tt = t * t, yt = y * t;
+        see = see + ee;
+        stt = stt + tt;
+        syt = syt + yt;
+        st = st + t;
+        emax = meas_max(emax, fabs(e));
+        const double ce = A.c * ep, ct = A.c * tp;
+        const double de = e - ce, dt = t - ct;
+        const double dee = de * de, dtt = dt * dt;
+        pee = pee + dee;
+        ptt = ptt + dtt;
+        ep = e;
+        tp = t;
+    }
+    a[0] = see; a[Pn] = stt; a[2 * Pn] = syt; a[3 * Pn] = st; a[4 * Pn] = emax; a[5 * Pn] = pee; a[6 * Pn] = ptt;
+    a[7 * Pn] = ep; a[8 * Pn] = tp;
+}
+
+// the target's plan: per wave of 64 pairs whether they share (which, row, lag) -- then the wave takes its target tile once
+template <class VI>
+inline void meas_target_plan(const int *which, const long long *lag, long long n, int nrows, VI *wuni) {
+    const long long Pn = n * nrows;
+    wuni->assign((size_t)((Pn + 63) / 64), 0);
+    for (long long w = 0; w * 64 < Pn; ++w) {
+        const long long i0 = w * 64 / nrows, j0 = w * 64 - i0 * nrows;
+        int u = 1;
+        for (long long q = w * 64; q < Pn && q < w * 64 + 64; ++q) {
+            const long long i = q / nrows;
+            if (q - i * nrows != j0 || which[i] != which[i0] || lag[i] != lag[i0]) u = 0;
+        }
+        (*wuni)[(size_t)w] = u;
+    }
+}
 
 // one unit of one pair over the chunk, sample after sample (the reference order every backend keeps)
 ACME_HD inline void meas_chain(const MeasArgs &A, long long p, int u) {
@@ -1012,7 +1090,128 @@ __global__ __launch_bounds__(256) void acme_meas_cross_kernel(acme::MeasCrossArg
         cy[(A.m0 + t) & (L - 1)] = yp[t * A.ny];
     }
 }
+
+// target: the moments unit's shape -- 64 pairs a block, a lane each, tiles of 64 pairs x MEAS_TILE samples of y staged through
+// LDS with loads along the samples, every wave reading its lane's column -- with the chains of a pair split over
+// MEAS_TARGET_WAVES waves (ROLE): 0 the error chains See, emax, Pee (carry e_prev), 1 the target chains Stt, St, Ptt (carry
+// t_prev, no read of y), 2 the one mixed chain Syt; two or three dependent fp64 additions per lane and sample.  The phase s is
+// formed once per lane and chunk in 64-bit integers and advanced by compare-and-wrap.  A UNIFORM wave (wuni: its pairs share
+// which, row and lag) takes the tile's 64 target values once, lane l that of sample l, and broadcasts the current one
+// (acme_meas_bcast: no memory access); any other wave gathers per lane, eight samples' loads ahead of the chains.  The values
+// and the order of every chain are meas_target_chain's.
+template <int ROLE>
+__device__ inline void acme_meas_target_step(double y, double t, double c, double &a0, double &a1, double &a2, double &pv) {
+    ACME_NO_CONTRACT
+    using namespace acme;
+    if (ROLE == 0) {
+        const double e = y - t;
+        const double ee = e * e;
+        a0 = a0 + ee;
+        a1 = meas_max(a1, fabs(e));
+        const double ce = c * pv;
+        const double de = e - ce;
+        const double dee = de * de;
+        a2 = a2 + dee;
+        pv = e;
+    } else if (ROLE == 1) {
+        const double tt = t * t;
+        a0 = a0 + tt;
+        a1 = a1 + t;
+        const double ct = c * pv;
+        const double dt = t - ct;
+        const double dtt = dt * dt;
+        a2 = a2 + dtt;
+        pv = t;
+    } else {
+        const double yt = y * t;
+        a0 = a0 + yt;
+    }
+}
+// one tile of nt samples: trow the lane's row of the y tile, tg the target row, s the phase of the tile's first sample (of the
+// lane's pair; uniform: of the wave's), advanced to the next tile's
+template <int ROLE>
+__device__ inline void acme_meas_target_tile(const double *trow, int nt, bool uni, const double *tg, long long &s, long long P,
+                                             double c, int lane, double &a0, double &a1, double &a2, double &pv) {
+    using namespace acme;
+    if (uni) {
+        long long q = s + lane;                         // (s < P, lane < 64)
+        if (P >= 64) { if (q >= P) q -= P; } else q = (long long)((int)q % (int)P);
+        const double tl = lane < nt ? tg[q] : 0.0;     // lane t holds sample t's target
+        if (nt == MEAS_TILE) {                          // (a whole tile: a fixed trip count the compiler unrolls)
+#pragma unroll 8
+            for (int t = 0; t < MEAS_TILE; ++t)
+                acme_meas_target_step<ROLE>(ROLE == 1 ? 0.0 : trow[t], acme_meas_bcast(tl, t), c, a0, a1, a2, pv);
+        } else {
+            for (int t = 0; t < nt; ++t)
+                acme_meas_target_step<ROLE>(ROLE == 1 ? 0.0 : trow[t], acme_meas_bcast(tl, t), c, a0, a1, a2, pv);
+        }
+        s += nt;
+        if (P >= 64) { if (s >= P) s -= P; } else s = (long long)((int)s % (int)P);
+        return;
+    }
+    int t = 0;
+    for (; t + 8 <= nt; t += 8) {
+        double tv[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {                  // the eight loads are in flight together
+            tv[k] = tg[s];
+            if (++s == P) s = 0;
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acme_meas_target_step<ROLE>(ROLE == 1 ? 0.0 : trow[t + k], tv[k], c, a0, a1, a2, pv);
+    }
+    for (; t < nt; ++t) {
+        const double tv = tg[s];
+        if (++s == P) s = 0;
+        acme_meas_target_step<ROLE>(ROLE == 1 ? 0.0 : trow[t], tv, c, a0, a1, a2, pv);
+    }
+}
+__global__ __launch_bounds__(64 * acme::MEAS_TARGET_WAVES) void acme_meas_target_kernel(acme::MeasTargetArgs A) {
+    using namespace acme;
+    __shared__ double tile[64][MEAS_TILE + 1];          // [pair][sample]: column reads by lane hit distinct banks
+    __shared__ long long base[64];                      // a pair's first element of the chunk in y
+    const int lane = threadIdx.x & 63, role = threadIdx.x >> 6;
+    const long long Pn = A.n * A.nrows, p0 = (long long)blockIdx.x * 64, p = p0 + lane;
+    const bool mine = p < Pn;
+    const bool uni = A.wuni[blockIdx.x] != 0;           // (wave-uniform: one value per block)
+    const long long pq = uni || !mine ? p0 : p;         // the pair whose target row and phase the lane walks (p0 < Pn)
+    const long long i = pq / A.nrows, j = pq - i * A.nrows;
+    if (threadIdx.x < 64 && mine) {
+        const long long ip = p / A.nrows;
+        base[lane] = (ip * A.pitch + A.t0) * A.ny + A.row[p - ip * A.nrows];
+    }
+    const double *tg = A.tgt + ((long long)A.which[i] * A.nrows + j) * A.P;
+    long long s = (A.m0 % A.P + A.lag[i]) % A.P;        // once per lane and chunk, in 64-bit integers
+    // the role's planes: 0 -- See, emax, Pee, e_prev; 1 -- Stt, St, Ptt, t_prev; 2 -- Syt
+    const int i0 = role == 0 ? 0 : role == 1 ? 1 : 2, i1 = role == 0 ? 4 : 3, i2 = role == 0 ? 5 : 6, i3 = role == 0 ? 7 : 8;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0, pv = 0.0;
+    if (mine && A.m0 != 0) {                            // (the window's first sample starts from 0.0 without reading)
+        a0 = A.acc[i0 * Pn + p];
+        if (role < 2) { a1 = A.acc[i1 * Pn + p]; a2 = A.acc[i2 * Pn + p]; pv = A.acc[i3 * Pn + p]; }
+    }
+    for (long long tb = 0; tb < A.len; tb += MEAS_TILE) {
+        const int nt = (int)(A.len - tb < MEAS_TILE ? A.len - tb : MEAS_TILE);
+        __syncthreads();                                // (the previous tile has been read by every wave)
+        for (int pp = role; pp < 64; pp += MEAS_TARGET_WAVES)   // wave pp: pair pp's samples, one per lane
+            if (p0 + pp < Pn && lane < nt) tile[pp][lane] = A.y[base[pp] + (tb + lane) * A.ny];
+        __syncthreads();
+        if (role == 0) acme_meas_target_tile<0>(tile[lane], nt, uni, tg, s, A.P, A.c, lane, a0, a1, a2, pv);
+        else if (role == 1) acme_meas_target_tile<1>(tile[lane], nt, uni, tg, s, A.P, A.c, lane, a0, a1, a2, pv);
+        else acme_meas_target_tile<2>(tile[lane], nt, uni, tg, s, A.P, A.c, lane, a0, a1, a2, pv);
+    }
+    if (mine) {
+        A.acc[i0 * Pn + p] = a0;
+        if (role < 2) { A.acc[i1 * Pn + p] = a1; A.acc[i2 * Pn + p] = a2; A.acc[i3 * Pn + p] = pv; }
+    }
+}
 namespace acme {
+inline int meas_target_launch(const MeasTargetArgs &A, hipStream_t st) {
+    const long long pairs = A.n * A.nrows;
+    if (pairs <= 0) return 0;
+    hipLaunchKernelGGL(acme_meas_target_kernel, dim3((unsigned)((pairs + 63) / 64)), dim3(64 * MEAS_TARGET_WAVES), 0, st, A);
+    return (int)hipGetLastError();
+}
+inline int meas_target_zero(double *p, size_t count) { return (int)hipMemset(p, 0, sizeof(double) * count); }
 template <int LOG2L>
 inline int meas_cross_launch_l(const MeasCrossArgs &C, hipStream_t st) {
     if constexpr (LOG2L > 12) {
@@ -1214,6 +1413,14 @@ inline int meas_cross_launch(const MeasCrossArgs &C, void *) {
     return 0;
 }
 inline int meas_cross_zero(double *p, size_t count) {
+    std::fill(p, p + count, 0.0);
+    return 0;
+}
+inline int meas_target_launch(const MeasTargetArgs &A, void *) {
+    for (long long p = 0; p < A.n * A.nrows; ++p) meas_target_chain(A, p);
+    return 0;
+}
+inline int meas_target_zero(double *p, size_t count) {
     std::fill(p, p + count, 0.0);
     return 0;
 }

@@ -71,12 +71,14 @@ ABI_SYMBOLS = [
     "acme_batch_get_measurement_spectrum_table",
     "acme_batch_set_measurement_cross", "acme_batch_get_measurement_cross", "acme_batch_get_measurement_cross_sums",
     "acme_batch_get_measurement_cross_table",
+    "acme_batch_set_measurement_target", "acme_batch_get_measurement_target",
 ]
 
 SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE, SOURCE_NOISE = 1, 2, 3, 4, 5
 NOISE_UNIFORM, NOISE_GAUSSIAN = 0, 1
 MAX_SOURCE_TONES = 4
 MAX_FOLD_PERIOD = 65536
+MAX_TARGETS = 64
 _SOURCE_KINDS = {"const": SOURCE_CONST, "sine": SOURCE_SINE, "table": SOURCE_TABLE, "multisine": SOURCE_MULTISINE, "noise": SOURCE_NOISE,
                  SOURCE_CONST: SOURCE_CONST, SOURCE_SINE: SOURCE_SINE, SOURCE_TABLE: SOURCE_TABLE, SOURCE_MULTISINE: SOURCE_MULTISINE,
                  SOURCE_NOISE: SOURCE_NOISE}
@@ -209,6 +211,8 @@ class Library:
         L.acme_batch_get_measurement_cross.argtypes = [vp, dp, lp, lp]
         L.acme_batch_get_measurement_cross_sums.argtypes = [vp, dp]
         L.acme_batch_get_measurement_cross_table.argtypes = [vp, dp, dp]
+        L.acme_batch_set_measurement_target.argtypes = [vp, dp, C.c_longlong, C.c_longlong, ip, lp, C.c_double]
+        L.acme_batch_get_measurement_target.argtypes = [vp, dp, lp]
 
     def check(self, rc):
         if rc < 0:
@@ -484,6 +488,63 @@ class MeasurementCross:
                    a.in_row, a.window, a.hop)
 
 
+class MeasurementTarget:
+    """What ``ModelRunner.measurement_target()`` returns: the residual of the measured window against the target waveform,
+    per instance and measured row.  ``sums`` (N, nrows, 7): the chains themselves in the order ``See, Stt, Syt, St, emax,
+    Pee, Ptt`` (also as ``see`` ... ``ptt``, (N, nrows) each); ``count`` the samples measured, ``rows`` the measured output
+    rows, ``y_mean`` (N, nrows) the base measurement's mean (None when read with ``raw=True``)."""
+    NAMES = ("see", "stt", "syt", "st", "emax", "pee", "ptt")
+
+    def __init__(self, sums, count, rows, y_mean=None):
+        self.sums, self.count, self.rows, self.y_mean = sums, int(count), tuple(rows), y_mean
+        for k, name in enumerate(self.NAMES):
+            setattr(self, name, sums[:, :, k])
+
+    @property
+    def esr(self):
+        """the error-to-signal ratio ``See / Stt`` = sum (y - t)^2 / sum t^2"""
+        return self.see / self.stt
+
+    @property
+    def esr_preemphasis(self):
+        """the error-to-signal ratio behind the pre-emphasis filter 1 - c z^-1, ``Pee / Ptt``"""
+        return self.pee / self.ptt
+
+    @property
+    def gain(self):
+        """the least-squares gain g of y = g t, ``Syt / Stt``"""
+        return self.syt / self.stt
+
+    @property
+    def error_rms(self):
+        return np.sqrt(self.see / self.count)
+
+    @property
+    def error_peak(self):
+        return self.emax
+
+    @property
+    def error_mean(self):
+        """the mean of y - t: the base measurement's mean of y less ``St / count``"""
+        if self.y_mean is None:
+            raise ValueError("error_mean needs the base measurement's mean: read measurement_target() without raw=True")
+        return self.y_mean - self.st / self.count
+
+    @property
+    def null_db(self):
+        """the depth of the null against the target, ``10 log10(See / Stt)`` (-inf: y == t sample for sample)"""
+        with np.errstate(divide="ignore"):
+            return 10.0 * np.log10(self.esr)
+
+    @classmethod
+    def concatenate(cls, parts):
+        a = parts[0]
+        if any((p.count, p.rows) != (a.count, a.rows) for p in parts):
+            raise ValueError("the shards' targets differ in their sample counts or measured rows")
+        ym = None if any(p.y_mean is None for p in parts) else np.concatenate([p.y_mean for p in parts])
+        return cls(np.concatenate([p.sums for p in parts]), a.count, a.rows, ym)
+
+
 def segment_window(nfft, window):
     """the ``window`` argument of ``set_measurement_spectrum`` / ``set_measurement_cross`` as the ABI takes it: "hann" (periodic),
     "rect" (None: all ones) or ``nfft`` values"""
@@ -619,6 +680,7 @@ class ModelRunner:
         self._fold = False              # a fold is set on the armed measurement
         self._spectrum = None           # (nfft, hop) of the spectrum set on the armed measurement
         self._cross = None              # (nfft, hop, in_row) of the cross-spectrum set on the armed measurement
+        self._target = False            # a target is set on the armed measurement
         self._sources = {}              # input row -> kind, while the row has a source
         self._sine = {}                 # input row -> (f_den, f_num as armed) of its sine source
         self._progress_cb = None
@@ -712,6 +774,7 @@ class ModelRunner:
         self._fold = False
         self._spectrum = None
         self._cross = None
+        self._target = False
         return self
 
     def set_measurement_bins(self, coef, start=0, length=0, rows=None, f_den=None, f_num=None, tones_from_source=None):
@@ -749,6 +812,7 @@ class ModelRunner:
         self._fold = False
         self._spectrum = None
         self._cross = None
+        self._target = False
         return self
 
     def measurement_plan(self):
@@ -772,6 +836,7 @@ class ModelRunner:
         self._fold = False
         self._spectrum = None
         self._cross = None
+        self._target = False
         return self
 
     def set_measurement_series(self, win, hop=None, windows=1):
@@ -929,6 +994,47 @@ class ModelRunner:
         sxy.real, sxy.imag = out[:, :, 2], out[:, :, 3]
         return MeasurementCross(out[:, :, 0].copy(), out[:, :, 1].copy(), sxy, seg.value, count.value, rows, in_row,
                                 self.measurement_cross_table()[0], hop)
+
+    def set_measurement_target(self, target, which=None, lag=None, preemphasis=0.0):
+        """Compare the armed measurement's window with a waveform of the caller's (``acme_batch_set_measurement_target``):
+        per instance and measured row the sums of (y - t)^2, t^2, y t and t, the peak |y - t| and, behind the pre-emphasis
+        filter 1 - ``preemphasis`` z^-1, the sums of the filtered error's and target's squares.  ``target``: (P,) -- one
+        looped waveform for every measured row --, (nrows, P) or (K, nrows, P), K <= 64 recordings; ``which``: N integers
+        (None: 0), the recording instance i is compared with; ``lag``: N integers 0 ... P - 1 (None: 0), instance i reads
+        the target ``lag[i]`` samples ahead.  Needs an armed measurement (any form, any window) that has not been fed yet;
+        not together with a series; ``measurement_target`` reads it."""
+        if self._meas is None:
+            raise AcmeError("no measurement is armed")
+        nrows = len(self._meas[1])
+        t = np.asarray(target, dtype=np.float64)
+        if t.ndim == 1:
+            t = np.broadcast_to(t, (1, nrows, t.shape[0]))
+        elif t.ndim == 2:
+            t = t[None]
+        if t.ndim != 3 or t.shape[1] != nrows:
+            raise DimensionMismatch(f"the target must have shape (P,), ({nrows}, P) or (K, {nrows}, P)")
+        t = np.ascontiguousarray(t)
+        for a, what in ((which, "which"), (lag, "lag")):
+            if a is not None and np.ndim(a) != 0 and np.shape(a) != (self.n,):
+                raise DimensionMismatch(f"per-instance {what} needs {self.n} values")
+        wa = None if which is None else np.ascontiguousarray(np.broadcast_to(np.asarray(which), (self.n,)), dtype=np.int32)
+        if wa is not None and not np.all(wa == np.asarray(which)):
+            raise DimensionMismatch("which must be integers")
+        la, lp = self._per_instance(lag, np.int64, "lag")
+        self.lib.check(self.lib.L.acme_batch_set_measurement_target(self.h, _dp(t), t.shape[0], t.shape[2],
+                                                                    None if wa is None else _ip(wa), lp, float(preemphasis)))
+        self._target = True
+        return self
+
+    def measurement_target(self, raw=False):
+        """the residual against the target so far (``acme_batch_get_measurement_target``): a ``MeasurementTarget``.  ``raw``:
+        the chains alone (``sums``; the tests pin them), without the read of the base measurement that ``error_mean`` needs."""
+        if self._meas is None or not self._target:
+            raise AcmeError("no measurement target is set")
+        rows = self._meas[1]
+        out, count = np.empty((self.n, len(rows), 7)), C.c_longlong(0)
+        self.lib.check(self.lib.L.acme_batch_get_measurement_target(self.h, _dp(out), C.byref(count)))
+        return MeasurementTarget(out, count.value, rows, None if raw else self.measurement().mean)
 
     def reset_measurement(self):
         """zero the accumulators and restart the window's clock (``acme_batch_reset_measurement``)"""
@@ -1604,6 +1710,22 @@ class MultiDeviceRunner:
     def measurement_cross(self, raw=False):
         """the shards' ``MeasurementCross`` results, concatenated along the instances (``raw`` as ``ModelRunner``'s)"""
         return MeasurementCross.concatenate([r.measurement_cross(raw) for r in self.runners if r is not None])
+
+    def set_measurement_target(self, target, which=None, lag=None, preemphasis=0.0):
+        """``ModelRunner.set_measurement_target`` on every device's batch, per-instance ``which`` and ``lag`` sliced over the
+        devices (every batch holds the whole table)"""
+        for a, what in ((which, "which"), (lag, "lag")):
+            if a is not None and np.ndim(a) != 0 and len(a) != self.n:
+                raise DimensionMismatch(f"per-instance {what} needs {self.n} values")
+        part = lambda a, lo, hi: a if a is None or np.ndim(a) == 0 else np.asarray(a)[lo:hi]
+        for r, (lo, hi) in zip(self.runners, self.ranges):
+            if r is not None:
+                r.set_measurement_target(target, part(which, lo, hi), part(lag, lo, hi), preemphasis)
+        return self
+
+    def measurement_target(self, raw=False):
+        """the shards' ``MeasurementTarget`` results, concatenated along the instances (``raw`` as ``ModelRunner``'s)"""
+        return MeasurementTarget.concatenate([r.measurement_target(raw) for r in self.runners if r is not None])
 
     def measure(self, u=None, check=True, T=None):
         """``run`` with y = NULL on every device (``u``: (N, T, nu), the ABI's layout); only the measurements are fed.

@@ -460,6 +460,51 @@ int acme_batch_get_measurement_cross(acme_batch *b, double *out, long long *segm
 int acme_batch_get_measurement_cross_sums(acme_batch *b, double *out);
 /* the window w[L] and the table tw[L / 2][2] the kernel uses (either may be NULL) */
 int acme_batch_get_measurement_cross_table(acme_batch *b, double *w, double *tw);
+/* A TARGET of the window: the armed measurement (any of the three forms, any start / length, no sample fed since arming or the
+ * last reset) also compares every measured row with a waveform the caller brings -- the residual y - t against a recording:
+ * the error-to-signal ratio sum (y - t)^2 / sum t^2 of N candidate parameter sets against the recorded output of the real
+ * device, plain and behind a first-order pre-emphasis filter; the null of a Monte-Carlo or potentiometer batch against the
+ * nominal waveform; a scan of integer alignments in one batch.  7 doubles per instance and measured row in place of
+ * y [N][T][ny].
+ *   t        HOST array [K][nrows][P] of K target waveforms, one per measured row in the ascending order of the measurement's
+ *            rows, P samples each, LOOPED; 1 <= K <= ACME_MAX_TARGETS, 1 <= P, K nrows P <= ACME_MAX_SOURCE_TABLE, every value
+ *            finite.  Copied to the device by the call.
+ *   which    HOST array [N] or NULL (every instance: target 0); 0 <= which[i] < K: the recording instance i is compared with
+ *            (the real device recorded at K knob positions, N = K x M candidates).
+ *   lag      HOST array [N] or NULL (every instance: 0); 0 <= lag[i] < P: instance i reads the target lag[i] samples ahead.
+ *   preemph  the pre-emphasis coefficient c, 0 <= c < 1, finite.
+ * Arithmetic, per instance i, j-th measured row and window sample m = n - start -- every product and every sum rounded on its
+ * own, NO fused multiply-add anywhere, every accumulator ONE chain in sample order from 0.0:
+ *   s   = (m + lag_i) mod P                      in 64-bit integers
+ *   t   = tgt[(which_i nrows + j) P + s]
+ *   e   = y - t
+ *   See = See + e e     Stt = Stt + t t     Syt = Syt + y t     St = St + t
+ *   emax = max(emax, |e|) from 0.0, NaN sticking exactly as the measurement's max does
+ *   de  = e - c e_prev      dt = t - c t_prev      (e_prev = t_prev = 0.0 at m = 0)
+ *   Pee = Pee + de de   Ptt = Ptt + dt dt   then e_prev = e, t_prev = t
+ * The result depends on nothing but the run's samples: chunk, slice and call boundaries, host or device memory, the entry point
+ * (acme_batch_run, _run_const, _run_async, _run_sources), the oversampling factor (y is the base-rate output after decimation)
+ * and whether y is stored change none of its bits; e_prev and t_prev live with the accumulators and carry across chunks, slices
+ * and calls.  Instance i of a per-instance arming reads, bit for bit, what a shared arming with which_i and lag_i reads.  With
+ * c = 0, Pee == See and Ptt == Stt bit for bit (finite y).  The measurement's own accumulators, plan, launches and getter are
+ * what they are without a target; the target takes one more kernel per chunk of the window and the table plus 9 doubles per
+ * pair of device memory.  A fold, a spectrum, a cross-spectrum and a target may all be set together.
+ * ACME_ERR_INVALID (the message names the argument, the instance of an entry of which or lag, the index of a non-finite target
+ * value): no measurement armed, samples already fed, t null, K, P or K nrows P out of range, a non-finite target value, a
+ * which[i] or lag[i] out of range, preemph out of range.  ACME_ERR_UNSUPPORTED together with a series, whichever is set first:
+ * a target per window is not available.  Setting a target again replaces the earlier one.  _reset_measurement zeroes the chains
+ * and the two carries and keeps the table, which, lag and c; arming any form or _clear_measurement removes the target;
+ * acme_batch_set_matrices carries it with the accumulators.  A batch without a target launches, allocates and synchronises
+ * what it always did. */
+#define ACME_MAX_TARGETS 64
+int acme_batch_set_measurement_target(acme_batch *b, const double *t /* host [K][nrows][P] */, long long K, long long P,
+                                      const int *which /* host [N] or NULL */, long long *lag /* host [N] or NULL, only read */,
+                                      double preemph);
+/* the chains so far, undivided: out[N][nrows][7] (may be NULL) in the order See, Stt, Syt, St, emax, Pee, Ptt (the tests pin
+ * them with ==; sums of separate runs can be added); *count: samples measured, as acme_batch_get_measurement counts them (may
+ * be NULL).  A window nothing has reached reads 0.0 with count 0.  ACME_ERR_INVALID without a target.  Joins a pending
+ * acme_batch_run_async and synchronises the device. */
+int acme_batch_get_measurement_target(acme_batch *b, double *out, long long *count);
 /* switch the measurement off (y = NULL is refused again) */
 int acme_batch_clear_measurement(acme_batch *b);
 /* zero the accumulators and restart the window's clock (the armed parameters stay) */

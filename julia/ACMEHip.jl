@@ -39,7 +39,7 @@ export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host
        set_source!, clear_source!, source_clock, source_clock!, run_sources!, render_sources,
        set_source_multisine!, set_source_noise!, set_measurement_bins!, set_measurement_series!, measurement_series,
        set_measurement_fold!, measurement_fold, set_measurement_spectrum!, measurement_spectrum,
-       set_measurement_cross!, measurement_cross
+       set_measurement_cross!, measurement_cross, set_measurement_target!, measurement_target
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
 
@@ -54,6 +54,7 @@ const ACME_MAX_HARMONICS = 32
 const ACME_MAX_SERIES_WINDOWS = 1048576
 const ACME_MIN_SPECTRUM = 64
 const ACME_MAX_SPECTRUM = 4096
+const ACME_MAX_TARGETS = 64
 const ACME_SOURCE_CONST, ACME_SOURCE_SINE, ACME_SOURCE_TABLE, ACME_SOURCE_MULTISINE = Cint(1), Cint(2), Cint(3), Cint(4)
 const ACME_SOURCE_NOISE = Cint(5)
 const ACME_NOISE_UNIFORM, ACME_NOISE_GAUSSIAN = Cint(0), Cint(1)
@@ -750,6 +751,54 @@ function measurement_cross(r::BatchRunner; sums::Bool=false)
     check(ccall((:acme_batch_get_measurement_cross_table, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}), r.h, window, table))
     return (sxx=out[:, 1, :, :], syy=out[:, 2, :, :], sxy=complex.(out[:, 3, :, :], out[:, 4, :, :]),
             segments=segments[], count=count[], window=window, table=table)
+end
+
+"""
+    set_measurement_target!(runner, target; which=nothing, lag=nothing, preemphasis=0.0)
+
+Compare the armed measurement's window with a waveform of the caller's (`acme_batch_set_measurement_target`): per instance
+and measured row the sums of (y - t)^2, t^2, y t and t, the peak |y - t| and, behind the pre-emphasis filter
+1 - `preemphasis` z^-1, the sums of the filtered error's and target's squares.  `target` is `P`, `P x nrows` or
+`P x nrows x K` (K <= 64 looped recordings, one waveform per measured row); `which::Vector` (0-based, one per
+instance, `nothing`: 0) selects the recording instance `i` is compared with, `lag::Vector` (0 ... P - 1, `nothing`: 0) the
+number of samples it reads the target ahead.  Needs an armed measurement that has not been fed yet; not together with a series.
+"""
+function set_measurement_target!(r::BatchRunner, target::AbstractArray{<:Real}; which=nothing, lag=nothing,
+                                 preemphasis::Real=0.0)
+    spec = r.meas
+    spec === nothing && error("no measurement is armed")
+    ny = ACME.ny(r.model)
+    nrows = spec.rows == 0 ? min(ny, 64) : count_ones(spec.rows)
+    t = convert(Array{Float64}, target)
+    ndims(t) == 1 && (t = repeat(t, 1, nrows))
+    ndims(t) == 2 && (t = reshape(t, size(t, 1), size(t, 2), 1))
+    (ndims(t) == 3 && size(t, 2) == nrows) || throw(DimensionMismatch("the target must be P, P x $nrows or P x $nrows x K"))
+    1 <= size(t, 3) <= ACME_MAX_TARGETS || throw(DimensionMismatch("1 ... $ACME_MAX_TARGETS targets"))
+    wh = perinstance(Cint, which, r.n)
+    lg = perinstance(Int64, lag, r.n)
+    GC.@preserve t wh lg check(ccall((:acme_batch_set_measurement_target, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Clonglong, Clonglong, Ptr{Cint}, Ptr{Clonglong}, Cdouble),
+                r.h, t, size(t, 3), size(t, 1), ptr_or_null(wh), ptr_or_null(lg), preemphasis))
+    return r
+end
+
+"""
+    measurement_target(runner) -> (see, stt, syt, st, emax, pee, ptt, count)
+
+The residual against the target so far (`acme_batch_get_measurement_target`): the seven chains, undivided, `nrows x N` each --
+the error-to-signal ratio is `see ./ stt`, behind the pre-emphasis `pee ./ ptt`, the least-squares gain `syt ./ stt` -- and
+the number of samples measured.
+"""
+function measurement_target(r::BatchRunner)
+    spec = r.meas
+    spec === nothing && error("no measurement is armed")
+    ny = ACME.ny(r.model)
+    nrows = spec.rows == 0 ? min(ny, 64) : count_ones(spec.rows)
+    count = Ref{Clonglong}(0)
+    out = Array{Float64,3}(undef, 7, nrows, r.n)                     # the ABI's [N][nrows][7]
+    check(ccall((:acme_batch_get_measurement_target, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Clonglong}), r.h, out, count))
+    return (see=out[1, :, :], stt=out[2, :, :], syt=out[3, :, :], st=out[4, :, :], emax=out[5, :, :], pee=out[6, :, :],
+            ptt=out[7, :, :], count=count[])
 end
 
 """
