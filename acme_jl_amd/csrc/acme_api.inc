@@ -192,6 +192,12 @@ struct acme_batch {
         int *d_tgt_which = nullptr, *d_tgt_wuni = nullptr;      // [N], [(N nrows + 63) / 64]: the plan (meas_target_plan)
         long long *d_tgt_lag = nullptr;          // [N]
         double *d_tgt_acc = nullptr;             // [9][N nrows]: the seven chains and the carries e_prev, t_prev, from 0.0
+        // weighting (acme_batch_set_measurement_weighting): a biquad cascade ahead of every form; wS = 0: none
+        int wS = 0;
+        double wsos[MEAS_MAX_WEIGHT_SECTIONS][5] = {};          // b0 b1 b2 a1 a2
+        double *d_wstate = nullptr;              // [2 wS][N nrows]: the sections' s1 and s2, from 0.0
+        double *d_yw = nullptr;                  // one slice of weighted rows, [N][n][nrows] (grow-only)
+        size_t cap_yw = 0;
     } meas;
     // Input rows generated on the device (acme_batch_set_source_*, acme_source.h): the rows' descriptions and per-instance
     // parameters in device memory, the source clock
@@ -807,6 +813,7 @@ static void meas_release(acme_batch::Measurement &M) {
     (void)be::dfree(M.d_spec_w); (void)be::dfree(M.d_spec_tw); (void)be::dfree(M.d_spec_acc); (void)be::dfree(M.d_spec_carry);
     (void)be::dfree(M.d_cross_w); (void)be::dfree(M.d_cross_tw); (void)be::dfree(M.d_cross_acc); (void)be::dfree(M.d_cross_carry);
     (void)be::dfree(M.d_tgt); (void)be::dfree(M.d_tgt_which); (void)be::dfree(M.d_tgt_wuni); (void)be::dfree(M.d_tgt_lag); (void)be::dfree(M.d_tgt_acc);
+    (void)be::dfree(M.d_wstate); (void)be::dfree(M.d_yw);
     M = acme_batch::Measurement{};
 }
 
@@ -1461,15 +1468,19 @@ static int os_grow(double **p, size_t *cap, size_t bytes) {
 }
 // the measurement step of n base-rate output samples (instance i, sample t, row r at y[(i * pitch + t) * ny + r]) that follow
 // the meas.pos samples since arming: the part inside the window [start, start + length), chunk by chunk.  u: the same n samples
-// of the base-rate input rows, complete (instance i, sample t, row r at u[(i * upitch + t) * nu + r]); the cross-spectrum reads it
-static int meas_step(acme_batch *b, const double *y, long long n, long long pitch, const double *u, long long upitch, be::stream_t st) {
+// of the base-rate input rows, complete (instance i, sample t, row r at u[(i * upitch + t) * nu + r]); the cross-spectrum reads it.
+// packed: y holds the measured rows alone, [N][pitch][nrows] (the weighted rows of meas_feed) -- ny = nrows, the identity row table
+static int meas_step(acme_batch *b, const double *y, long long n, long long pitch, const double *u, long long upitch, be::stream_t st,
+                     bool packed = false) {
     acme_batch::Measurement &M = b->meas;
+    unsigned char row[64];
+    for (int r = 0; r < 64; ++r) row[r] = packed ? (unsigned char)r : M.row[r];
     const long long end = M.W ? M.start + (M.W - 1) * M.hop + M.win : M.length ? M.start + M.length : LLONG_MAX;
     const long long lo = M.pos > M.start ? M.pos : M.start, hi = M.pos + n < end ? M.pos + n : end;
     for (long long s = lo; M.nrows > 0 && s < hi; s += M.chunk) {
         const long long len = hi - s < M.chunk ? hi - s : M.chunk;
-        MeasArgs A{y, M.d_acc, M.d_tw, b->N, len, pitch, s - M.pos, b->P.actual.ny, M.nrows, M.H, {}};
-        memcpy(A.row, M.row, sizeof(A.row));
+        MeasArgs A{y, M.d_acc, M.d_tw, b->N, len, pitch, s - M.pos, packed ? M.nrows : b->P.actual.ny, M.nrows, M.H, {}};
+        memcpy(A.row, row, sizeof(A.row));
         if (M.W) {      // a series: the chunk's table and ONE kernel, whatever windows the chunk holds
             const MeasSeries S{M.win, M.hop, M.W, s - M.start};
             const MeasSeriesTwArgs W{M.d_tw, M.bins ? M.d_kbin_g : M.pi ? M.d_fnum_g : nullptr, M.f_num, M.f_den, len, S, M.H,
@@ -1489,29 +1500,53 @@ static int meas_step(acme_batch *b, const double *y, long long n, long long pitc
         }
         if (M.fold) {   // one more kernel on the same chunk of y
             MeasFoldArgs G{y, M.d_fold, M.d_fold_per, b->N, len, pitch, s - M.pos, s - M.start, M.fold_pmax, A.ny, M.nrows, {}};
-            memcpy(G.row, M.row, sizeof(G.row));
+            memcpy(G.row, row, sizeof(G.row));
             HIPCHK(meas_fold_launch(G, st));
         }
         if (M.spec) {   // ... and the segments that end in this chunk
             MeasSpecArgs G{y, M.d_spec_acc, M.d_spec_carry, M.d_spec_w, M.d_spec_tw, b->N, len, pitch, s - M.pos, s - M.start,
                            M.spec_L, M.spec_hop, A.ny, M.nrows, {}};
-            memcpy(G.row, M.row, sizeof(G.row));
+            memcpy(G.row, row, sizeof(G.row));
             HIPCHK(meas_spectrum_launch(G, st));
         }
         if (M.cross) {  // ... and those segments of the input row beside the measured rows
             MeasCrossArgs G{{y, M.d_cross_acc, M.d_cross_carry, M.d_cross_w, M.d_cross_tw, b->N, len, pitch, s - M.pos, s - M.start,
                              M.cross_L, M.cross_hop, A.ny, M.nrows, {}}, u, upitch, b->P.actual.nu, M.cross_in};
-            memcpy(G.S.row, M.row, sizeof(G.S.row));
+            memcpy(G.S.row, row, sizeof(G.S.row));
             HIPCHK(meas_cross_launch(G, st));
         }
         if (M.target) { // ... and the residual against the target on the same chunk
             MeasTargetArgs G{y, M.d_tgt_acc, M.d_tgt, M.d_tgt_which, M.d_tgt_lag, M.d_tgt_wuni, b->N, len, pitch, s - M.pos, s - M.start,
                              M.tgt_P, M.tgt_c, A.ny, M.nrows, {}};
-            memcpy(G.row, M.row, sizeof(G.row));
+            memcpy(G.row, row, sizeof(G.row));
             HIPCHK(meas_target_launch(G, st));
         }
     }
     M.pos += n;
+    return ACME_OK;
+}
+// what a slice hands to the measurement: meas_step on its outputs, or -- a weighting is set -- on the weighted measured rows.
+// The cascade runs over every sample since arming (its states carry from slice to slice), one kernel per stretch of at most
+// os_slice samples into meas.d_yw, and meas_step reads that packed array; the cross-spectrum's u is the slice's own.  Once the
+// window has ended nothing reads the weighted signal any more and the filter stops with it.
+static int meas_feed(acme_batch *b, const double *y, long long n, long long pitch, const double *u, long long upitch, be::stream_t st) {
+    acme_batch::Measurement &M = b->meas;
+    if (!M.wS || M.nrows == 0) return meas_step(b, y, n, pitch, u, upitch, st);
+    const long long end = M.W ? M.start + (M.W - 1) * M.hop + M.win : M.length ? M.start + M.length : LLONG_MAX;
+    if (M.pos >= end) { M.pos += n; return ACME_OK; }
+    const int ny = b->P.actual.ny, nu = b->P.actual.nu;
+    const long long WS = os_slice(n);
+    const int rc = os_grow(&M.d_yw, &M.cap_yw, sizeof(double) * (size_t)b->N * (size_t)WS * (size_t)M.nrows);
+    if (rc != ACME_OK) return rc;
+    for (long long off = 0; off < n; off += WS) {
+        const long long len = n - off < WS ? n - off : WS;
+        MeasWeightArgs G{y + off * ny, M.d_yw, M.d_wstate, b->N, len, pitch, ny, M.nrows, M.wS, {}, {}};
+        memcpy(G.sos, M.wsos, sizeof(G.sos));
+        memcpy(G.row, M.row, sizeof(G.row));
+        HIPCHK(meas_weight_launch(G, st));
+        const int rs = meas_step(b, M.d_yw, len, len, u ? u + off * nu : nullptr, upitch, st, true);
+        if (rs != ACME_OK) return rs;
+    }
     return ACME_OK;
 }
 // u: [N][T][nu], or -- const_mask != 0 -- the varying rows [N][T][nuv] and u_const [N][nu] (acme_batch_run_const); y: [N][T][ny],
@@ -1593,7 +1628,7 @@ static int run_os(acme_batch *b, const double *u, const double *u_const, unsigne
             O.fresh = false;
         }
         if (scatter) HIPCHK(src_launch_copy(SrcCopyArgs{y + (size_t)s * TS * ny, dst, (long long)N, n, T, ny}, st));
-        return M.on ? meas_step(b, dst, n, ypitch, src, pitch, st) : ACME_OK;
+        return M.on ? meas_feed(b, dst, n, ypitch, src, pitch, st) : ACME_OK;
     };
     if (!host) {
         for (long long s = 0; s < ns; ++s) {
@@ -2185,6 +2220,10 @@ static int meas_zero(acme_batch *b) {
         HIPCHK(meas_target_zero(M.d_tgt_acc, P * (size_t)MEAS_TARGET_SLOTS));
         HIPCHK(be::device_sync());
     }
+    if (M.wS) {         // the sections' states (the coefficients stay)
+        HIPCHK(meas_weight_zero(M.d_wstate, P * 2 * (size_t)M.wS));
+        HIPCHK(be::device_sync());
+    }
     M.pos = 0;
     return ACME_OK;
 }
@@ -2730,6 +2769,43 @@ int acme_batch_get_measurement_target(acme_batch *b, double *out, long long *cou
     if (!a.empty()) HIPCHK(be::copy_d2h(a.data(), M.d_tgt_acc, sizeof(double) * a.size()));
     for (size_t p = 0; p < pairs; ++p)
         for (int k = 0; k < 7; ++k) out[p * 7 + k] = a[(size_t)k * pairs + p];
+    return ACME_OK;
+}
+
+int acme_batch_set_measurement_weighting(acme_batch *b, const double *sos, int S) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    acme_batch::Measurement &M = b->meas;
+    if (!M.on) return fail(ACME_ERR_INVALID, "measurement weighting: no measurement is armed");
+    if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement weighting: samples have been fed since arming (arm or reset the measurement first)");
+    if (!sos) return fail(ACME_ERR_INVALID, "measurement weighting: sos is null");
+    if (S < 1 || S > MEAS_MAX_WEIGHT_SECTIONS)
+        return fail(ACME_ERR_INVALID, "measurement weighting: S is outside 1 ... " + std::to_string(MEAS_MAX_WEIGHT_SECTIONS));
+    for (int k = 0; k < 5 * S; ++k)
+        if (!std::isfinite(sos[k]))
+            return fail(ACME_ERR_INVALID, "measurement weighting: sos[" + std::to_string(k / 5) + "][" + std::to_string(k % 5) + "] is not finite");
+    const size_t states = (size_t)b->N * M.nrows * 2 * (size_t)S;
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    (void)be::dfree(M.d_wstate);        // (a weighting set again replaces the earlier one)
+    M.d_wstate = nullptr;
+    M.wS = 0;
+    HIPCHK(be::dmalloc((void **)&M.d_wstate, sizeof(double) * std::max<size_t>(states, 1)));
+    HIPCHK(meas_weight_zero(M.d_wstate, states));
+    HIPCHK(be::device_sync());
+    memset(M.wsos, 0, sizeof(M.wsos));
+    memcpy(M.wsos, sos, sizeof(double) * 5 * (size_t)S);
+    M.wS = S;
+    return ACME_OK;
+}
+
+int acme_batch_get_measurement_weighting(acme_batch *b, double *sos, int *S) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const acme_batch::Measurement &M = b->meas;
+    if (!M.on || !M.wS) return fail(ACME_ERR_INVALID, "no measurement weighting is set");
+    if (S) *S = M.wS;
+    if (sos) memcpy(sos, M.wsos, sizeof(M.wsos));
     return ACME_OK;
 }
 

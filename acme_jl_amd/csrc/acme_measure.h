@@ -87,6 +87,14 @@
 // of a pair split over three waves, a wave whose pairs share (which, row, lag) -- decided on the host at arming,
 // meas_target_plan -- broadcasting its target tile, any other gathering per lane; the emulator walks meas_target_chain.
 //
+// WEIGHTING (acme_batch_set_measurement_weighting): a cascade of S <= 8 second-order sections, transposed direct form II, ahead
+// of every form above -- per pair and sample, section after section, v = b0 x + s1, s1 = (b1 x - a1 v) + s2, s2 = b2 x - a2 v,
+// x <- v, no fused multiply-add.  It runs on every base-rate output sample since arming; the states are [2 S][N nrows] (plane
+// 2 k: s1 of section k, 2 k + 1: s2).  ONE kernel per slice (acme_meas_weight_kernel<S>) writes the weighted rows packed,
+// [N][len][nrows], and every measurement kernel then reads that array with ny = nrows and the identity row table: the
+// moments unit's tiles, four waves staging jointly through two LDS buffers, the next tile's loads in flight while the first
+// wave walks the current tile's chains in place; the emulator walks meas_weight_chain.
+//
 // The per-element functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with g++).
 #pragma once
@@ -358,6 +366,49 @@ inline void meas_target_plan(const int *which, const long long *lag, long long n
         }
         (*wuni)[(size_t)w] = u;
     }
+}
+
+// weighting: the slice's n base-rate samples of every measured row through the cascade, the weighted samples packed
+constexpr int MEAS_MAX_WEIGHT_SECTIONS = 8;
+constexpr int MEAS_WEIGHT_WAVES = 4;        // the waves of a block that stage a tile jointly (acme_meas_weight_kernel)
+
+struct MeasWeightArgs {
+    const double *y;            // instance i, sample t, row r at y[(i * pitch + t) * ny + r]
+    double *w;                  // [n][len][nrows]: instance i, sample t, j-th measured row at w[(i * len + t) * nrows + j]
+    double *state;              // [2 S][n * nrows]: plane 2 k the s1 of section k, plane 2 k + 1 its s2
+    long long n, len, pitch;
+    int ny, nrows, S;
+    double sos[MEAS_MAX_WEIGHT_SECTIONS][5];    // b0 b1 b2 a1 a2
+    unsigned char row[64];      // the measured rows, ascending
+};
+
+// one section on one sample: the contract's four lines (every product and every sum rounded on its own)
+ACME_HD ACME_NO_CONTRACT_FN inline double meas_weight_section(const double *c, double x, double &s1, double &s2) {
+    ACME_NO_CONTRACT
+    const double b0x = c[0] * x;
+    const double v = b0x + s1;
+    const double b1x = c[1] * x, a1v = c[3] * v;
+    const double d1 = b1x - a1v;
+    s1 = d1 + s2;
+    const double b2x = c[2] * x, a2v = c[4] * v;
+    s2 = b2x - a2v;
+    return v;
+}
+
+// one pair over the slice, sample after sample: the contract of include/acme_hip.h as a plain loop (the reference order every
+// backend keeps)
+ACME_HD inline void meas_weight_chain(const MeasWeightArgs &A, long long p) {
+    const long long Pn = A.n * A.nrows, i = p / A.nrows, j = p - i * A.nrows;
+    const double *yp = A.y + i * A.pitch * A.ny + A.row[j];
+    double *wp = A.w + i * A.len * A.nrows + j;
+    double s1[MEAS_MAX_WEIGHT_SECTIONS], s2[MEAS_MAX_WEIGHT_SECTIONS];
+    for (int k = 0; k < A.S; ++k) { s1[k] = A.state[2 * k * Pn + p]; s2[k] = A.state[(2 * k + 1) * Pn + p]; }
+    for (long long t = 0; t < A.len; ++t) {
+        double x = yp[t * A.ny];
+        for (int k = 0; k < A.S; ++k) x = meas_weight_section(A.sos[k], x, s1[k], s2[k]);
+        wp[t * A.nrows] = x;
+    }
+    for (int k = 0; k < A.S; ++k) { A.state[2 * k * Pn + p] = s1[k]; A.state[(2 * k + 1) * Pn + p] = s2[k]; }
 }
 
 // one unit of one pair over the chunk, sample after sample (the reference order every backend keeps)
@@ -1204,7 +1255,122 @@ __global__ __launch_bounds__(64 * acme::MEAS_TARGET_WAVES) void acme_meas_target
         if (role < 2) { A.acc[i1 * Pn + p] = a1; A.acc[i2 * Pn + p] = a2; A.acc[i3 * Pn + p] = pv; }
     }
 }
+
+// weighting: 64 pairs a block, a lane each, tiles of 64 pairs x MEAS_TILE samples.  The MEAS_WEIGHT_WAVES waves stage
+// jointly: wave q loads, writes to LDS and stores the SAME sixteen pairs' rows (loads and stores along the samples), so a
+// buffer's reuse by its rows' owner is ordered inside that wave and ONE barrier per tile is enough -- tile k + 1's loads are
+// issued, wave 0 walks tile k's chains in place in its buffer (a lane per pair, a column of the padded tile; the sections of the
+// cascade unrolled in the lane, S a template argument so that the states are registers), the loaded rows go to the other
+// buffer, barrier, every wave stores its rows of tile k.  The values and their order are meas_weight_chain's.
+template <int S>
+__global__ __launch_bounds__(64 * acme::MEAS_WEIGHT_WAVES) void acme_meas_weight_kernel(acme::MeasWeightArgs A) {
+    using namespace acme;
+    constexpr int PW = 64 / MEAS_WEIGHT_WAVES;          // pairs a wave stages
+    __shared__ double tile[2][64][MEAS_TILE + 1];       // [buffer][pair][sample]: column reads by lane hit distinct banks
+    __shared__ long long base[64], wbase[64];           // a pair's first element of the slice in y and in w
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long Pn = A.n * A.nrows, p0 = (long long)blockIdx.x * 64, p = p0 + lane;
+    const bool mine = p < Pn, chain = wave == 0 && mine;
+    if (threadIdx.x < 64 && mine) {
+        const long long ip = p / A.nrows, j = p - ip * A.nrows;
+        base[lane] = ip * A.pitch * A.ny + A.row[j];
+        wbase[lane] = ip * A.len * A.nrows + j;
+    }
+    double c[S][5];                                     // the coefficients in vector registers: 10 S scalar ones do not fit
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+#pragma unroll
+        for (int q = 0; q < 5; ++q) {
+            double v = A.sos[k][q];
+            asm volatile("" : "+v"(v));
+            c[k][q] = v;
+        }
+    }
+    double s1[S], s2[S];
+#pragma unroll
+    for (int k = 0; k < S; ++k) {
+        s1[k] = chain ? A.state[2 * k * Pn + p] : 0.0;
+        s2[k] = chain ? A.state[(2 * k + 1) * Pn + p] : 0.0;
+    }
+    __syncthreads();
+    const int npair = (int)(Pn - p0 < 64 ? Pn - p0 : 64);       // the block's pairs
+    double r[PW];
+#pragma unroll
+    for (int q = 0; q < PW; ++q) {                      // tile 0
+        const int pp = wave * PW + q;
+        r[q] = pp < npair && lane < A.len ? A.y[base[pp] + (long long)lane * A.ny] : 0.0;
+    }
+#pragma unroll
+    for (int q = 0; q < PW; ++q) tile[0][wave * PW + q][lane] = r[q];
+    __syncthreads();
+    int buf = 0;
+    for (long long tb = 0; tb < A.len; tb += MEAS_TILE, buf ^= 1) {
+        const int nt = (int)(A.len - tb < MEAS_TILE ? A.len - tb : MEAS_TILE);
+        const long long tn = tb + MEAS_TILE;            // the next tile's first sample
+        const bool more = tn < A.len;
+        if (more) {                                     // its loads are in flight during this tile's chains
+#pragma unroll
+            for (int q = 0; q < PW; ++q) {
+                const int pp = wave * PW + q;
+                r[q] = pp < npair && tn + lane < A.len ? A.y[base[pp] + (tn + lane) * A.ny] : 0.0;
+            }
+        }
+        if (chain) {
+            double *trow = tile[buf][lane];
+            if (nt == MEAS_TILE) {                      // (a whole tile: a fixed trip count the compiler unrolls)
+#pragma unroll 8
+                for (int t = 0; t < MEAS_TILE; ++t) {
+                    double x = trow[t];
+#pragma unroll
+                    for (int k = 0; k < S; ++k) x = meas_weight_section(c[k], x, s1[k], s2[k]);
+                    trow[t] = x;
+                }
+            } else {
+                for (int t = 0; t < nt; ++t) {
+                    double x = trow[t];
+#pragma unroll
+                    for (int k = 0; k < S; ++k) x = meas_weight_section(c[k], x, s1[k], s2[k]);
+                    trow[t] = x;
+                }
+            }
+        }
+        if (more) {
+#pragma unroll
+            for (int q = 0; q < PW; ++q) tile[buf ^ 1][wave * PW + q][lane] = r[q];
+        }
+        __syncthreads();                                // (this tile's chains are done, the next tile is in LDS)
+#pragma unroll
+        for (int q = 0; q < PW; ++q) {
+            const int pp = wave * PW + q;
+            if (pp < npair && lane < nt) A.w[wbase[pp] + (tb + lane) * A.nrows] = tile[buf][pp][lane];
+        }
+    }
+    if (chain) {
+#pragma unroll
+        for (int k = 0; k < S; ++k) { A.state[2 * k * Pn + p] = s1[k]; A.state[(2 * k + 1) * Pn + p] = s2[k]; }
+    }
+}
 namespace acme {
+template <int S>
+inline int meas_weight_launch_s(const MeasWeightArgs &A, hipStream_t st) {
+    hipLaunchKernelGGL(acme_meas_weight_kernel<S>, dim3((unsigned)((A.n * A.nrows + 63) / 64)), dim3(64 * MEAS_WEIGHT_WAVES), 0, st, A);
+    return (int)hipGetLastError();
+}
+inline int meas_weight_launch(const MeasWeightArgs &A, hipStream_t st) {
+    if (A.n * A.nrows <= 0 || A.len <= 0) return 0;
+    switch (A.S) {
+    case 1: return meas_weight_launch_s<1>(A, st);
+    case 2: return meas_weight_launch_s<2>(A, st);
+    case 3: return meas_weight_launch_s<3>(A, st);
+    case 4: return meas_weight_launch_s<4>(A, st);
+    case 5: return meas_weight_launch_s<5>(A, st);
+    case 6: return meas_weight_launch_s<6>(A, st);
+    case 7: return meas_weight_launch_s<7>(A, st);
+    case 8: return meas_weight_launch_s<8>(A, st);
+    }
+    return (int)hipErrorInvalidValue;
+}
+inline int meas_weight_zero(double *p, size_t count) { return (int)hipMemset(p, 0, sizeof(double) * count); }
 inline int meas_target_launch(const MeasTargetArgs &A, hipStream_t st) {
     const long long pairs = A.n * A.nrows;
     if (pairs <= 0) return 0;
@@ -1413,6 +1579,14 @@ inline int meas_cross_launch(const MeasCrossArgs &C, void *) {
     return 0;
 }
 inline int meas_cross_zero(double *p, size_t count) {
+    std::fill(p, p + count, 0.0);
+    return 0;
+}
+inline int meas_weight_launch(const MeasWeightArgs &A, void *) {
+    for (long long p = 0; p < A.n * A.nrows; ++p) meas_weight_chain(A, p);
+    return 0;
+}
+inline int meas_weight_zero(double *p, size_t count) {
     std::fill(p, p + count, 0.0);
     return 0;
 }

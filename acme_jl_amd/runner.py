@@ -72,6 +72,7 @@ ABI_SYMBOLS = [
     "acme_batch_set_measurement_cross", "acme_batch_get_measurement_cross", "acme_batch_get_measurement_cross_sums",
     "acme_batch_get_measurement_cross_table",
     "acme_batch_set_measurement_target", "acme_batch_get_measurement_target",
+    "acme_batch_set_measurement_weighting", "acme_batch_get_measurement_weighting",
 ]
 
 SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE, SOURCE_NOISE = 1, 2, 3, 4, 5
@@ -79,6 +80,7 @@ NOISE_UNIFORM, NOISE_GAUSSIAN = 0, 1
 MAX_SOURCE_TONES = 4
 MAX_FOLD_PERIOD = 65536
 MAX_TARGETS = 64
+MAX_WEIGHTING_SECTIONS = 8
 _SOURCE_KINDS = {"const": SOURCE_CONST, "sine": SOURCE_SINE, "table": SOURCE_TABLE, "multisine": SOURCE_MULTISINE, "noise": SOURCE_NOISE,
                  SOURCE_CONST: SOURCE_CONST, SOURCE_SINE: SOURCE_SINE, SOURCE_TABLE: SOURCE_TABLE, SOURCE_MULTISINE: SOURCE_MULTISINE,
                  SOURCE_NOISE: SOURCE_NOISE}
@@ -213,6 +215,8 @@ class Library:
         L.acme_batch_get_measurement_cross_table.argtypes = [vp, dp, dp]
         L.acme_batch_set_measurement_target.argtypes = [vp, dp, C.c_longlong, C.c_longlong, ip, lp, C.c_double]
         L.acme_batch_get_measurement_target.argtypes = [vp, dp, lp]
+        L.acme_batch_set_measurement_weighting.argtypes = [vp, dp, C.c_int]
+        L.acme_batch_get_measurement_weighting.argtypes = [vp, dp, C.POINTER(C.c_int)]
 
     def check(self, rc):
         if rc < 0:
@@ -278,6 +282,12 @@ class Measurement:
     def peak(self):
         return np.maximum(np.abs(self.min), np.abs(self.max))
 
+    def loudness(self):
+        """the window's loudness ``-0.691 + 10 log10(sum y^2 / count)`` (N, nrows), LKFS when the measurement carries the K
+        weighting (``weighting_sos("K", fs)``) and the window is a 400 ms block of BS.1770"""
+        with np.errstate(divide="ignore"):
+            return -0.691 + 10.0 * np.log10(self.rms * self.rms)
+
     def thd(self):
         """total harmonic distortion sqrt(sum_{h >= 2} |A_h|^2) / |A_1| (N, nrows); needs H >= 2"""
         a = np.abs(self.harmonics)
@@ -330,6 +340,20 @@ class MeasurementSeries:
     @property
     def peak(self):
         return np.maximum(np.abs(self.min), np.abs(self.max))
+
+    def loudness(self, blocks=1):
+        """the loudness ``-0.691 + 10 log10(sum y^2 / count)`` per window (W, N, nrows), as ``Measurement.loudness``.
+        ``blocks`` > 1: of every run of ``blocks`` consecutive windows taken together (W - blocks + 1, N, nrows), for a series
+        of back-to-back windows (``hop == win``; a series does not take overlapping windows) -- behind the K weighting,
+        windows of 100 ms with ``blocks=4`` are the 400 ms blocks every 100 ms of BS.1770.  Complete windows only."""
+        ms = self.rms * self.rms
+        if blocks > 1:
+            if self.hop != self.win:
+                raise ValueError("loudness over several windows needs a series of back-to-back windows (hop == win)")
+            n = len(ms) - blocks + 1
+            ms = sum(ms[k:k + max(n, 0)] for k in range(blocks)) / blocks
+        with np.errstate(divide="ignore"):
+            return -0.691 + 10.0 * np.log10(ms)
 
     def thd(self):
         """total harmonic distortion per window (W, N, nrows); needs H >= 2"""
@@ -545,6 +569,111 @@ class MeasurementTarget:
         return cls(np.concatenate([p.sums for p in parts]), a.count, a.rows, ym)
 
 
+class MeasurementWeighting:
+    """What ``ModelRunner.measurement_weighting()`` returns, and what ``set_measurement_weighting`` accepts: a cascade of
+    second-order sections, ``sos`` (S, 5) with the rows ``b0 b1 b2 a1 a2`` of
+    H(z) = (b0 + b1 z^-1 + b2 z^-2) / (1 + a1 z^-1 + a2 z^-2)."""
+
+    def __init__(self, sos):
+        self.sos = sos_rows(sos)
+
+    def apply(self, x):
+        """the cascade on ``x`` along its last axis from rest, in the arithmetic of ``acme_batch_set_measurement_weighting``
+        (transposed direct form II, every product and sum rounded on its own): bit for bit what the device's measurement
+        reads for an output ``x``.  Weight a target recording with it before ``set_measurement_target``."""
+        x = np.array(x, dtype=np.float64)
+        w = np.empty_like(x)
+        s1 = np.zeros((len(self.sos),) + x.shape[:-1])
+        s2 = np.zeros_like(s1)
+        with np.errstate(invalid="ignore", over="ignore"):
+            for t in range(x.shape[-1]):
+                v = x[..., t]
+                for k, (b0, b1, b2, a1, a2) in enumerate(self.sos):
+                    xk = v
+                    v = b0 * xk + s1[k]
+                    s1[k] = (b1 * xk - a1 * v) + s2[k]
+                    s2[k] = b2 * xk - a2 * v
+                w[..., t] = v
+        return w
+
+    def response(self, f, fs):
+        """the complex frequency response at the frequencies ``f`` (Hz) for the sample rate ``fs``"""
+        z1 = np.exp(-2j * np.pi * np.asarray(f, dtype=np.float64) / fs)
+        h = np.ones_like(z1)
+        for b0, b1, b2, a1, a2 in self.sos:
+            h = h * ((b0 + b1 * z1 + b2 * z1 * z1) / (1.0 + a1 * z1 + a2 * z1 * z1))
+        return h
+
+
+def sos_rows(sos):
+    """second-order sections as the ABI takes them, (S, 5) ``b0 b1 b2 a1 a2``: from (S, 5), or from scipy's (S, 6)
+    ``b0 b1 b2 a0 a1 a2`` whose ``a0`` must be 1.0 exactly"""
+    if isinstance(sos, MeasurementWeighting):
+        return sos.sos
+    a = np.asarray(sos, dtype=np.float64)
+    if a.ndim == 1 and a.shape[0] in (5, 6):
+        a = a[None]
+    if a.ndim != 2 or a.shape[1] not in (5, 6) or not 1 <= a.shape[0] <= MAX_WEIGHTING_SECTIONS:
+        raise DimensionMismatch(f"second-order sections must have shape (S, 5) or (S, 6), S = 1 ... {MAX_WEIGHTING_SECTIONS}")
+    if a.shape[1] == 6:
+        if not np.all(a[:, 3] == 1.0):
+            raise ValueError("second-order sections in the six-column layout must have a0 == 1.0 (normalise them first)")
+        a = a[:, [0, 1, 2, 4, 5]]
+    return np.ascontiguousarray(a)
+
+
+def _bilinear_section(num, den, fs):
+    """(n2, n1, n0) / (d2, d1, d0) in s -> b0 b1 b2 a1 a2 by s = 2 fs (1 - z^-1) / (1 + z^-1), no pre-warping"""
+    c = 2.0 * fs
+    poly = lambda n2, n1, n0: np.array([n2 * c * c + n1 * c + n0, 2.0 * n0 - 2.0 * n2 * c * c, n2 * c * c - n1 * c + n0])
+    b, a = poly(*num), poly(*den)
+    return np.concatenate([b / a[0], a[1:] / a[0]])
+
+
+# IEC 61672-1: the poles of the A and C weightings (Hz)
+_F1, _F2, _F3, _F4 = 20.598997, 107.65265, 737.86223, 12194.217
+
+
+def weighting_sos(kind, fs, r=0.995):
+    """Second-order sections (S, 5) for ``set_measurement_weighting`` at the sample rate ``fs``:
+
+    ``"A"``, ``"C"``  the IEC 61672 frequency weightings: the plain bilinear transform of the analog poles (20.6 Hz and
+               12 194 Hz double, for A also 107.7 Hz and 737.9 Hz), WITHOUT pre-warping, scaled to |H| = 1 at 1 kHz.  S = 3 / 2.
+    ``"K"``    the pre-filter of ITU-R BS.1770: the high shelf and the high-pass from their analog parameters by the usual
+               tan(pi f0 / fs) formulas; at 48 kHz the standard's coefficient tables.  S = 2.
+    ``"dc"``   the DC blocker (1 - z^-1) / (1 - r z^-1).  S = 1.
+
+    What the plain bilinear transform costs near Nyquist: the response at f is the analog one at (fs / pi) tan(pi f / fs),
+    so at 44.1 kHz the A curve reads -4.0 dB at 10 kHz where the analog curve reads -2.5 dB (48 kHz: -3.7 dB); below a few
+    kHz the two agree closely.  A caller who needs the analog curve to the top of the band brings a design of their own --
+    any (S, 5) or scipy-layout (S, 6) array is accepted."""
+    fs = float(fs)
+    if kind in ("A", "C"):
+        w1, w2, w3, w4 = (2.0 * np.pi * f for f in (_F1, _F2, _F3, _F4))
+        secs = [_bilinear_section((1.0, 0.0, 0.0), (1.0, 2.0 * w1, w1 * w1), fs)]
+        if kind == "A":
+            secs.append(_bilinear_section((1.0, 0.0, 0.0), (1.0, w2 + w3, w2 * w3), fs))
+        secs.append(_bilinear_section((0.0, 0.0, 1.0), (1.0, 2.0 * w4, w4 * w4), fs))
+        sos = np.array(secs)
+        sos[0, :3] /= abs(MeasurementWeighting(sos).response(1000.0, fs))
+        return sos
+    if kind == "K":
+        f0, G, Q = 1681.974450955533, 3.999843853973347, 0.7071752369554196
+        K = np.tan(np.pi * f0 / fs)
+        Vh = 10.0 ** (G / 20.0)
+        Vb = Vh ** 0.4996667741545416
+        a0 = 1.0 + K / Q + K * K
+        shelf = [(Vh + Vb * K / Q + K * K) / a0, 2.0 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0,
+                 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]
+        f0, Q = 38.13547087602444, 0.5003270373238773
+        K = np.tan(np.pi * f0 / fs)
+        a0 = 1.0 + K / Q + K * K
+        return np.array([shelf, [1.0, -2.0, 1.0, 2.0 * (K * K - 1.0) / a0, (1.0 - K / Q + K * K) / a0]])
+    if kind == "dc":
+        return np.array([[1.0, -1.0, 0.0, -float(r), 0.0]])
+    raise ValueError('weighting_sos: kind must be "A", "C", "K" or "dc"')
+
+
 def segment_window(nfft, window):
     """the ``window`` argument of ``set_measurement_spectrum`` / ``set_measurement_cross`` as the ABI takes it: "hann" (periodic),
     "rect" (None: all ones) or ``nfft`` values"""
@@ -681,6 +810,7 @@ class ModelRunner:
         self._spectrum = None           # (nfft, hop) of the spectrum set on the armed measurement
         self._cross = None              # (nfft, hop, in_row) of the cross-spectrum set on the armed measurement
         self._target = False            # a target is set on the armed measurement
+        self._weighting = False         # a weighting is set on the armed measurement
         self._sources = {}              # input row -> kind, while the row has a source
         self._sine = {}                 # input row -> (f_den, f_num as armed) of its sine source
         self._progress_cb = None
@@ -775,6 +905,7 @@ class ModelRunner:
         self._spectrum = None
         self._cross = None
         self._target = False
+        self._weighting = False
         return self
 
     def set_measurement_bins(self, coef, start=0, length=0, rows=None, f_den=None, f_num=None, tones_from_source=None):
@@ -813,6 +944,7 @@ class ModelRunner:
         self._spectrum = None
         self._cross = None
         self._target = False
+        self._weighting = False
         return self
 
     def measurement_plan(self):
@@ -837,6 +969,7 @@ class ModelRunner:
         self._spectrum = None
         self._cross = None
         self._target = False
+        self._weighting = False
         return self
 
     def set_measurement_series(self, win, hop=None, windows=1):
@@ -1035,6 +1168,28 @@ class ModelRunner:
         out, count = np.empty((self.n, len(rows), 7)), C.c_longlong(0)
         self.lib.check(self.lib.L.acme_batch_get_measurement_target(self.h, _dp(out), C.byref(count)))
         return MeasurementTarget(out, count.value, rows, None if raw else self.measurement().mean)
+
+    def set_measurement_weighting(self, sos):
+        """Put a cascade of second-order sections ahead of the armed measurement (``acme_batch_set_measurement_weighting``):
+        every form -- the window's moments and harmonics, bins, a series, a fold, a spectrum, a cross-spectrum's output
+        rows, a target's error -- then reads the weighted output, filtered from the first sample after arming on.  ``sos``:
+        (S, 5) rows ``b0 b1 b2 a1 a2`` or scipy's (S, 6) with ``a0 == 1.0``, S <= 8, or a ``MeasurementWeighting``;
+        ``weighting_sos`` makes the A, C and K curves and a DC blocker.  Needs an armed measurement that has not been fed
+        yet; ``measurement_weighting`` reads it back."""
+        if self._meas is None:
+            raise AcmeError("no measurement is armed")
+        a = sos_rows(sos)
+        self.lib.check(self.lib.L.acme_batch_set_measurement_weighting(self.h, _dp(a), a.shape[0]))
+        self._weighting = True
+        return self
+
+    def measurement_weighting(self):
+        """the weighting of the armed measurement (``acme_batch_get_measurement_weighting``): a ``MeasurementWeighting``"""
+        if self._meas is None or not self._weighting:
+            raise AcmeError("no measurement weighting is set")
+        out, S = np.zeros((MAX_WEIGHTING_SECTIONS, 5)), C.c_int(0)
+        self.lib.check(self.lib.L.acme_batch_get_measurement_weighting(self.h, _dp(out), C.byref(S)))
+        return MeasurementWeighting(out[:S.value].copy())
 
     def reset_measurement(self):
         """zero the accumulators and restart the window's clock (``acme_batch_reset_measurement``)"""
@@ -1726,6 +1881,17 @@ class MultiDeviceRunner:
     def measurement_target(self, raw=False):
         """the shards' ``MeasurementTarget`` results, concatenated along the instances (``raw`` as ``ModelRunner``'s)"""
         return MeasurementTarget.concatenate([r.measurement_target(raw) for r in self.runners if r is not None])
+
+    def set_measurement_weighting(self, sos):
+        """``ModelRunner.set_measurement_weighting`` on every device's batch: the same cascade everywhere"""
+        for r in self.runners:
+            if r is not None:
+                r.set_measurement_weighting(sos)
+        return self
+
+    def measurement_weighting(self):
+        """the cascade the shards share: a ``MeasurementWeighting``"""
+        return next(r for r in self.runners if r is not None).measurement_weighting()
 
     def measure(self, u=None, check=True, T=None):
         """``run`` with y = NULL on every device (``u``: (N, T, nu), the ABI's layout); only the measurements are fed.

@@ -505,6 +505,43 @@ int acme_batch_set_measurement_target(acme_batch *b, const double *t /* host [K]
  * be NULL).  A window nothing has reached reads 0.0 with count 0.  ACME_ERR_INVALID without a target.  Joins a pending
  * acme_batch_run_async and synchronises the device. */
 int acme_batch_get_measurement_target(acme_batch *b, double *out, long long *count);
+/* A WEIGHTING ahead of the measurement: the armed measurement (any form -- single window, per instance, bins, a series, with
+ * or without a fold, a spectrum, a cross-spectrum, a target --, no sample fed since arming or the last reset) reads every
+ * measured row through one cascade of S second-order sections, shared by all instances and rows: a band limit ahead of a
+ * THD+N reading, A, C or ITU-R 468 weighting ahead of a noise level, the K filter of BS.1770 ahead of the mean squares of a
+ * series of 400 ms blocks, a DC blocker ahead of any RMS, a pre-emphasis of the caller's ahead of the target's error-to-signal
+ * ratio -- none of which needs y [N][T][ny] stored.
+ *   sos      HOST array [S][5], per section b0 b1 b2 a1 a2 of H(z) = (b0 + b1 z^-1 + b2 z^-2) / (1 + a1 z^-1 + a2 z^-2) (a0 = 1);
+ *            every value finite.  Copied by the call.
+ *   S        1 ... ACME_MAX_WEIGHTING_SECTIONS
+ * The filter runs on EVERY base-rate output sample since arming, from sample 0 and not only inside the window (a transient has
+ * decayed by `start`), after the decimation of an oversampled batch.  Arithmetic, transposed direct form II, per instance,
+ * measured row, sample x = y and section k = 0 ... S - 1 in order -- every product and every sum rounded on its own, NO fused
+ * multiply-add, the parentheses as written:
+ *   v  = b0 x + s1
+ *   s1 = (b1 x - a1 v) + s2
+ *   s2 = b2 x - a2 v
+ *   x  = v                                       for the next section
+ * with s1 = s2 = 0.0 at arming and at a reset; the last section's v is the weighted sample w.  Subnormals are kept (the kernel
+ * leaves the fp64 denormal mode alone); a NaN sticks in the states of its own (instance, row) pair and touches no other.
+ * Every form reads w where it read y: the moments, min and max, the harmonics and bins, the windows of a series, the slots of
+ * a fold, the segments of a spectrum and of a cross-spectrum, the target's e = w - t.  The INPUT row of a cross-spectrum stays
+ * unweighted: H then includes the weighting's response, the coherence is what it is without a weighting.  The target's t is
+ * compared as brought (weight a recording on the host with the same arithmetic first).  A stored y is the raw output.
+ * The result depends on nothing but the run's samples: chunk, slice and call boundaries, host or device memory, the entry
+ * point, the oversampling factor and whether y is stored change none of its bits; the states live with the accumulators and
+ * carry across chunks, slices and calls.  The weighting takes one more kernel per slice, one slice of weighted rows
+ * [N][n][nrows] and 2 S doubles per pair of device memory; the measurement kernels are what they are without it.
+ * ACME_ERR_INVALID (the message names the argument, and the entry of a non-finite coefficient): no measurement armed, samples
+ * already fed, sos null, S out of range, a non-finite coefficient.  Setting a weighting again replaces the earlier one.
+ * _reset_measurement zeroes the states and keeps the coefficients; arming any form or _clear_measurement removes the
+ * weighting; acme_batch_set_matrices carries it with the accumulators.  A batch without a weighting launches, allocates and
+ * synchronises what it always did. */
+#define ACME_MAX_WEIGHTING_SECTIONS 8
+int acme_batch_set_measurement_weighting(acme_batch *b, const double *sos /* host [S][5]: b0 b1 b2 a1 a2 */, int S);
+/* the cascade as set: sos[8][5] (may be NULL; the rows from S on are 0.0) and *S (may be NULL).  ACME_ERR_INVALID without a
+ * weighting. */
+int acme_batch_get_measurement_weighting(acme_batch *b, double *sos /* [8][5] or NULL */, int *S);
 /* switch the measurement off (y = NULL is refused again) */
 int acme_batch_clear_measurement(acme_batch *b);
 /* zero the accumulators and restart the window's clock (the armed parameters stay) */

@@ -39,7 +39,8 @@ export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host
        set_source!, clear_source!, source_clock, source_clock!, run_sources!, render_sources,
        set_source_multisine!, set_source_noise!, set_measurement_bins!, set_measurement_series!, measurement_series,
        set_measurement_fold!, measurement_fold, set_measurement_spectrum!, measurement_spectrum,
-       set_measurement_cross!, measurement_cross, set_measurement_target!, measurement_target
+       set_measurement_cross!, measurement_cross, set_measurement_target!, measurement_target,
+       set_measurement_weighting!, measurement_weighting
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
 
@@ -55,6 +56,7 @@ const ACME_MAX_SERIES_WINDOWS = 1048576
 const ACME_MIN_SPECTRUM = 64
 const ACME_MAX_SPECTRUM = 4096
 const ACME_MAX_TARGETS = 64
+const ACME_MAX_WEIGHTING_SECTIONS = 8
 const ACME_SOURCE_CONST, ACME_SOURCE_SINE, ACME_SOURCE_TABLE, ACME_SOURCE_MULTISINE = Cint(1), Cint(2), Cint(3), Cint(4)
 const ACME_SOURCE_NOISE = Cint(5)
 const ACME_NOISE_UNIFORM, ACME_NOISE_GAUSSIAN = Cint(0), Cint(1)
@@ -799,6 +801,41 @@ function measurement_target(r::BatchRunner)
     check(ccall((:acme_batch_get_measurement_target, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Clonglong}), r.h, out, count))
     return (see=out[1, :, :], stt=out[2, :, :], syt=out[3, :, :], st=out[4, :, :], emax=out[5, :, :], pee=out[6, :, :],
             ptt=out[7, :, :], count=count[])
+end
+
+"""
+    set_measurement_weighting!(runner, sos)
+
+Put a cascade of second-order sections ahead of the armed measurement (`acme_batch_set_measurement_weighting`): every form
+then reads the weighted output, filtered from the first sample after arming on (transposed direct form II, no fused
+multiply-add).  `sos` is `S x 5` with the rows `b0 b1 b2 a1 a2`, or `S x 6` in the layout `b0 b1 b2 a0 a1 a2` with
+`a0 == 1`; `S <= 8`.  Needs an armed measurement that has not been fed yet.
+"""
+function set_measurement_weighting!(r::BatchRunner, sos::AbstractMatrix{<:Real})
+    r.meas === nothing && error("no measurement is armed")
+    a = convert(Matrix{Float64}, sos)
+    if size(a, 2) == 6
+        all(a[:, 4] .== 1.0) || throw(ArgumentError("second-order sections with six columns must have a0 == 1"))
+        a = a[:, [1, 2, 3, 5, 6]]
+    end
+    (size(a, 2) == 5 && 1 <= size(a, 1) <= ACME_MAX_WEIGHTING_SECTIONS) ||
+        throw(DimensionMismatch("second-order sections must be S x 5 or S x 6, S = 1 ... $ACME_MAX_WEIGHTING_SECTIONS"))
+    t = Matrix{Float64}(transpose(a))                                # the ABI's [S][5]
+    GC.@preserve t check(ccall((:acme_batch_set_measurement_weighting, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Cint),
+                               r.h, t, size(a, 1)))
+    return r
+end
+
+"""
+    measurement_weighting(runner) -> Matrix{Float64}
+
+The cascade of the armed measurement as set (`acme_batch_get_measurement_weighting`): `S x 5`, the rows `b0 b1 b2 a1 a2`.
+"""
+function measurement_weighting(r::BatchRunner)
+    S = Ref{Cint}(0)
+    out = zeros(Float64, 5, ACME_MAX_WEIGHTING_SECTIONS)             # the ABI's [8][5]
+    check(ccall((:acme_batch_get_measurement_weighting, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ref{Cint}), r.h, out, S))
+    return Matrix{Float64}(transpose(out[:, 1:S[]]))
 end
 
 """
