@@ -1370,10 +1370,11 @@ template <class S, int MODE = MODE_RUN, bool LOW = false> ACME_DEV void wave_mai
         }
     };
     // evaluate! on the reduced system: q' = pf' + fq' z_N, (res, Jq) = elements(q'), S row = Jq row * fq'.  Leaves the S row
-    // in a[NL ..], the residual in res, the right-hand side of the elimination in rhs.  off (offany: any instance of the
-    // wave): this iterate may lie off the linear rows' subspace -- the elements see the full q = pfull + fq z, the step
-    // corrects for the difference, and lres is the lane's linear residual (lanes < NL).
-    auto evaluate_c = [&](double zz, bool offany, bool off) ACME_LAMBDA {
+    // in a[NL ..], the residual in res, the right-hand side of the elimination in rhs.  off (bit 8 of the lane's offw;
+    // offany: any instance of the wave): this iterate may lie off the linear rows' subspace -- the elements see the full
+    // q = pfull + fq z, the step corrects for the difference, and lres is the lane's linear residual (lanes < NL).
+    // (offw is the caller's flag word as it stands: the bit is looked at only where offany has been taken)
+    auto evaluate_c = [&](double zz, bool offany, int offw) ACME_LAMBDA {
         if constexpr (COND) {
             double urc[14];
             sfor<0, 7>([&](auto pc) ACME_LAMBDA {
@@ -1389,6 +1390,7 @@ template <class S, int MODE = MODE_RUN, bool LOW = false> ACME_DEV void wave_mai
                 wv::fmac_bcast_chain_from<NL, NR, t == 0>(e[t], zz, cd[t]);
             });
             if (ACME_RARE(offany)) {
+                const bool off = (offw & 8) != 0;
                 double fqv[NT][NNr + 1], ef[NT];
                 load_fq_rows(fqv);
                 sfor<0, NT>([&](auto tc_) ACME_LAMBDA { ef[decltype(tc_)::value] = pf[decltype(tc_)::value]; });
@@ -1417,7 +1419,7 @@ template <class S, int MODE = MODE_RUN, bool LOW = false> ACME_DEV void wave_mai
             if (ACME_RARE(offany)) {
                 double c_ = 0.0;
                 sfor<0, NT>([&](auto tc_) ACME_LAMBDA { c_ = fma(tv[decltype(tc_)::value], de[decltype(tc_)::value], c_); });
-                corr = (off && !islin) ? c_ : 0.0;
+                corr = ((offw & 8) != 0 && !islin) ? c_ : 0.0;
             }
         }
     };
@@ -1429,23 +1431,33 @@ template <class S, int MODE = MODE_RUN, bool LOW = false> ACME_DEV void wave_mai
     // their order (relearn_c) and repeats the pass.  Nothing in here assigns what the Newton loop only reads (cd, pf',
     // the lanes' rows): kept inside the loop, the re-learning made them loop-carried values with one register copy
     // each -- 30 of them -- per iteration.
-    auto lin_c = [&](double zz, bool act, unsigned long long actm, bool force, bool &small, double &dz, bool offany, bool off) ACME_LAMBDA -> bool {
-        bool mine = false;
+    // In two parts, so that the Newton loop can choose its bookkeeping between them.  lin_head returns `viol`: the lanes
+    // whose pivots failed, of the instances whose result is used -- wave-uniform, zero on the usual pass, and then `mine` is
+    // false for every instance: nothing that follows from it needs expanding per lane.  lin_tail takes `mine` and records.
+    auto lin_head = [&](double zz, bool act, unsigned long long actm, bool force, bool &small, double &dz, bool offany, int offw,
+                        bool &want, bool &recording) ACME_LAMBDA -> unsigned long long {
+        unsigned long long viol = 0ull;
         if constexpr (COND) {
-            evaluate_c(zz, offany, off);
+            evaluate_c(zz, offany, offw);
             ACME_T(TB_EVAL);
             unsigned long long big = wv::ballot(!(fabs(res) < tol_v)) & rows4(((1ull << NN) - 1ull) & ~((1ull << NL) - 1ull));
-            if (ACME_RARE(offany)) big |= wv::ballot(off && islin && !(fabs(lres) < tol_v));     // (off the subspace, the linear rows count)
+            if (ACME_RARE(offany)) big |= wv::ballot((offw & 8) != 0 && islin && !(fabs(lres) < tol_v));     // (off the subspace, the linear rows count)
             small = ((big >> (grp * GROUP)) & 0xFFFFull) == 0ull;
-            const bool want = force || (act && small);
+            want = force || (act && small);
             dz = res;
             if (ACME_RARE(offany)) dz = res - corr;
             double none[1] = {0.0}, dinv = 0.0;
-            const bool recording = wv::ballot(want) != 0ull;
-            unsigned long long viol = LU::template solve_range<NL, NN, 0, true, S>(a, dz, none, ojp, want && lig < NN, dinv);
-            viol &= actm | wv::ballot(force);
-            mine = ((viol >> (grp * GROUP)) & 0xFFFFull) != 0ull;
+            // (ballot(want), put together from masks that exist: the ballot of a conjunction goes through a vector register)
+            const unsigned long long usedm = actm | wv::ballot(force);
+            recording = ((wv::ballot(small) & actm) | wv::ballot(force)) != 0ull;
+            viol = LU::template solve_range<NL, NN, 0, true, S>(a, dz, none, ojp, want && lig < NN, dinv);
+            viol &= usedm;
             ACME_T(TB_GJP);
+        }
+        return viol;
+    };
+    auto lin_tail = [&](bool want, bool recording, bool mine) ACME_LAMBDA {
+        if constexpr (COND) {
             if (recording) {
                 if (want && !mine && lig < NN)
                     sfor<(NR + 1) / 2, S::OSLOTS / 2>([&](auto cc) ACME_LAMBDA {
@@ -1462,14 +1474,20 @@ template <class S, int MODE = MODE_RUN, bool LOW = false> ACME_DEV void wave_mai
             }
             ACME_T(TB_STORE);
         }
+    };
+    auto lin_c = [&](double zz, bool act, unsigned long long actm, bool force, bool &small, double &dz, bool offany, int offw) ACME_LAMBDA -> bool {
+        bool want = false, recording = false;
+        const unsigned long long viol = lin_head(zz, act, actm, force, small, dz, offany, offw, want, recording);
+        const bool mine = ((viol >> (grp * GROUP)) & 0xFFFFull) != 0ull;
+        lin_tail(want, recording, mine);
         return mine;
     };
     // the instances with `who` re-learn the order of their reduced system's rows: the reference's partially pivoted LU
     // (src/solvers.jl:58-78) on S at zz, just to find the pivot order, which the lanes adopt.  false: S is singular.
-    auto relearn_c = [&](double zz, bool who, bool offany, bool off) ACME_LAMBDA -> bool {
+    auto relearn_c = [&](double zz, bool who, bool offany, int offw) ACME_LAMBDA -> bool {
         bool okp = true;
         if constexpr (COND) {
-            evaluate_c(zz, offany, off);
+            evaluate_c(zz, offany, offw);
             int orig;
             okp = LU::template pivot_order_range<NL, NN>(a, orig, lig, grp);
             orig = who ? orig : lig;
@@ -1709,39 +1727,65 @@ template <class S, int MODE = MODE_RUN, bool LOW = false> ACME_DEV void wave_mai
             LU::template apply_loaded_from<NL, NR>(t, cmul);
             z = sel(need, lz - t, z);
             z = sel(need && mv, z0m, z);
-            fl = wv::keepi((need ? 1 : 0) | ((need && (osub != 0 || mv)) ? 8 : 0));
+            const bool off0 = need && (osub != 0 || mv);
+            fl = wv::keepi((need ? 1 : 0) | (off0 ? 8 : 0));
+            // What the usual pass never meets, as two wave masks carried across the loop: the lanes whose pass is `off` (flag 8)
+            // and those that have re-learnt their order for this pass (flag 32).  Only the general glue below changes these
+            // flags, so only it brings the masks up to date.
+            unsigned long long offm = wv::ballot(off0), rlm = 0ull;
             its = 0;
             ACME_T(TB_SETUP);
+            unsigned long long actm = wv::ballot((fl & 1) != 0);
             for (;;) {
-                unsigned long long actm = wv::ballot((fl & 1) != 0), redo = 0ull;
-                bool retry = false;
+                bool act, small, want, recording;
+                double dz;
+                unsigned long long viol;
+                // The usual passes, as a loop of their own: every active instance's pivots hold (mine, retry, stop_bad are
+                // false) and no lane holds flag 8 or 32 (nothing to carry into 16, nothing to clear).  Its bookkeeping is the
+                // general glue's statements with those constants folded in: the same values, a quarter of the instructions.
+                // Anything else leaves it with the pass's results for the general glue below, which sits outside so that the
+                // usual pass ends in its own loop test instead of a join of the two.
                 do {
-                    const bool act = (fl & 1) != 0, off = (fl & 8) != 0;
-                    bool small;
-                    double dz;
-                    const bool mine = lin_c(z, act, actm, false, small, dz, wv::ballot(off) != 0ull, off);
-                    retry = act && mine && (fl & 32) == 0;                 // first failure of the pivots in place: re-learn, repeat
-                    const bool stop_bad = act && mine && !retry;           // (src/solvers.jl:219-224: J singular or not finite)
-                    const bool want = act && !mine && small;
-                    const bool step = act && !mine && !want;
-                    its += (act && !retry) ? 1 : 0;
+                    act = wv::lanes(actm);
+                    viol = lin_head(z, act, actm, false, small, dz, offm != 0ull, fl, want, recording);
+                    if (ACME_RARE((viol | offm | rlm) != 0ull)) break;
+                    lin_tail(want, true, false);        // (no lane with `want`: nothing is stored, nothing changes)
+                    const bool step = act && !small;
+                    its += act ? 1 : 0;
                     z = sel(step, fma(sgn, z, -dz), z);
                     int nf = fl;
-                    nf = stop_bad ? ((nf & ~3) | (small ? 2 : 0)) : nf;      // hasconverged is the residual test alone (:203)
-                    nf = want ? ((nf & ~1) | 4 | ((nf & 8) ? 16 : 0)) : nf;
+                    nf = want ? ((nf & ~1) | 4) : nf;
                     nf = (step && !(its < maxiter_v)) ? (nf & ~1) : nf;
-                    nf = retry ? (small ? (nf | 64) : (nf & ~64)) : (nf & ~(8 | 32));     // (a pass that went through: the next failure re-learns again)
                     fl = wv::keepi(nf);
-                    redo = wv::ballot(retry);
                     ACME_T(TB_GLUE);
-                    if (ACME_RARE(redo != 0ull)) break;
                 } while ((actm = wv::ballot((fl & 1) != 0)) != 0ull);
-                if (ACME_USUAL(redo == 0ull)) break;
-                const bool off = retry && (fl & 8) != 0;
-                const bool okp = relearn_c(z, retry, wv::ballot(off) != 0ull, off);
-                // (exactly singular S: setlhs! fails and the solve returns at once, src/solvers.jl:223-224 -- that pass counts)
-                its += (retry && !okp) ? 1 : 0;
-                fl = wv::keepi(retry ? (okp ? (fl | 32) : ((fl & ~3) | ((fl & 64) ? 2 : 0))) : fl);
+                if (ACME_USUAL(actm == 0ull)) break;        // (a pass leaves the loop above only with active instances)
+                const bool mine = ((viol >> (grp * GROUP)) & 0xFFFFull) != 0ull;
+                lin_tail(want, recording, mine);
+                const bool retry = act && mine && (fl & 32) == 0;          // first failure of the pivots in place: re-learn, repeat
+                const bool stop_bad = act && mine && !retry;               // (src/solvers.jl:219-224: J singular or not finite)
+                const bool keepit = act && !mine && small;
+                const bool step = act && !mine && !keepit;
+                its += (act && !retry) ? 1 : 0;
+                z = sel(step, fma(sgn, z, -dz), z);
+                int nf = fl;
+                nf = stop_bad ? ((nf & ~3) | (small ? 2 : 0)) : nf;          // hasconverged is the residual test alone (:203)
+                nf = keepit ? ((nf & ~1) | 4 | ((nf & 8) ? 16 : 0)) : nf;
+                nf = (step && !(its < maxiter_v)) ? (nf & ~1) : nf;
+                nf = retry ? (small ? (nf | 64) : (nf & ~64)) : (nf & ~(8 | 32));     // (a pass that went through: the next failure re-learns again)
+                fl = wv::keepi(nf);
+                ACME_T(TB_GLUE);
+                if (ACME_RARE(wv::ballot(retry) != 0ull)) {
+                    const int offw = retry ? (fl & 8) : 0;
+                    const bool okp = relearn_c(z, retry, wv::ballot(offw != 0) != 0ull, offw);
+                    // (exactly singular S: setlhs! fails and the solve returns at once, src/solvers.jl:223-224 -- that pass counts)
+                    its += (retry && !okp) ? 1 : 0;
+                    fl = wv::keepi(retry ? (okp ? (fl | 32) : ((fl & ~3) | ((fl & 64) ? 2 : 0))) : fl);
+                }
+                offm = wv::ballot((fl & 8) != 0);
+                rlm = wv::ballot((fl & 32) != 0);
+                actm = wv::ballot((fl & 1) != 0);
+                if (actm == 0ull) break;
             }
             const bool accepted = (fl & 4) != 0;
             // the accepted iterate's z_L: what the linear rows give for its z_N (the lanes' last "residual" is exactly
@@ -1826,8 +1870,8 @@ template <class S, int MODE = MODE_RUN, bool LOW = false> ACME_DEV void wave_mai
                 if (wv::ballot(reorig) != 0ull) {
                     bool s0;
                     double d0;
-                    const bool roff = reorig && osub != 0;
-                    const unsigned long long roffany = wv::ballot(roff);
+                    const int roff = (reorig && osub != 0) ? 8 : 0;
+                    const unsigned long long roffany = wv::ballot(roff != 0);
                     const bool mine0 = lin_c(reorig ? lz : z, false, 0ull, reorig, s0, d0, roffany != 0ull, roff);
                     if (ACME_RARE(wv::ballot(mine0 && reorig) != 0ull)) {      // the lanes' order fails at the origin: re-learn it there
                         (void)relearn_c(reorig ? lz : z, mine0 && reorig, roffany != 0ull, roff);
@@ -1847,7 +1891,7 @@ template <class S, int MODE = MODE_RUN, bool LOW = false> ACME_DEV void wave_mai
                     // t_L = Jq_L dpfull through A_LL^-1 (u_L), the others' corrected by J_NL u_L (through pfull, as
                     // fq_L u_L), then the origin's recorded reduced elimination with the linear rows riding along.
                     // Jq at the origin from the FULL q (an `off` evaluation at last_z).
-                    evaluate_c(lz, true, mv);
+                    evaluate_c(lz, true, mv ? 8 : 0);
                     const wv::pair_t h_ = wv::ld2(&rd.rc[3 * 2 * GROUP]);
                     const double tvT[3] = {islin ? 1.0 : tv[0], islin ? crw : tv[1], islin ? h_.lo * efl1 : tv[2]};
                     double dp[3], tt = 0.0;

@@ -782,7 +782,7 @@ class ModelRunner:
     """
 
     def __init__(self, model, n_instances=1, showprogress=False, device=None, models=None,
-                 lib=None):
+                 lib=None, maxiter=None):
         if not isinstance(model, DiscreteModel):
             raise TypeError("model must be a DiscreteModel")
         self.lib = lib or default_library()
@@ -799,6 +799,8 @@ class ModelRunner:
         o.solver = SOLVER_IDS[model.solver]
         o.device = -1 if device is None else int(device)
         o.per_instance_matrices = 1 if models is not None else 0
+        if maxiter is not None:         # Newton iterations per base solve (``Options.maxiter``; None: the library's default)
+            o.maxiter = int(maxiter)
         h = C.c_void_p()
         self.lib.check(self.lib.L.acme_batch_create(self._mh.h, self.n, C.byref(o), C.byref(h)))
         self.h = h
