@@ -192,6 +192,14 @@ struct acme_batch {
         int *d_tgt_which = nullptr, *d_tgt_wuni = nullptr;      // [N], [(N nrows + 63) / 64]: the plan (meas_target_plan)
         long long *d_tgt_lag = nullptr;          // [N]
         double *d_tgt_acc = nullptr;             // [9][N nrows]: the seven chains and the carries e_prev, t_prev, from 0.0
+        // ensemble (acme_batch_set_measurement_ensemble): per-sample statistics across the instances of a group
+        bool ens = false;
+        int ens_G = 0;
+        long long ens_stride = 0, ens_E = 0;     // E = ceil(length / stride) slots
+        std::vector<long long> ens_off;          // [G + 1]: the plan's offsets on the host (the getter's members)
+        int *d_ens_member = nullptr;             // the plan (meas_ensemble_plan): instances sorted by (group, instance)
+        long long *d_ens_off = nullptr;          // [G + 1]
+        double *d_ens_acc = nullptr;             // [6][G nrows][E]: S, Q, min, max, then imin, imax as long long
         // weighting (acme_batch_set_measurement_weighting): a biquad cascade ahead of every form; wS = 0: none
         int wS = 0;
         double wsos[MEAS_MAX_WEIGHT_SECTIONS][5] = {};          // b0 b1 b2 a1 a2
@@ -814,6 +822,7 @@ static void meas_release(acme_batch::Measurement &M) {
     (void)be::dfree(M.d_cross_w); (void)be::dfree(M.d_cross_tw); (void)be::dfree(M.d_cross_acc); (void)be::dfree(M.d_cross_carry);
     (void)be::dfree(M.d_tgt); (void)be::dfree(M.d_tgt_which); (void)be::dfree(M.d_tgt_wuni); (void)be::dfree(M.d_tgt_lag); (void)be::dfree(M.d_tgt_acc);
     (void)be::dfree(M.d_wstate); (void)be::dfree(M.d_yw);
+    (void)be::dfree(M.d_ens_member); (void)be::dfree(M.d_ens_off); (void)be::dfree(M.d_ens_acc);
     M = acme_batch::Measurement{};
 }
 
@@ -1521,6 +1530,14 @@ static int meas_step(acme_batch *b, const double *y, long long n, long long pitc
             memcpy(G.row, row, sizeof(G.row));
             HIPCHK(meas_target_launch(G, st));
         }
+        if (M.ens) {    // ... and the statistics across the groups' instances at the chunk's recorded samples
+            const size_t plane = (size_t)M.ens_G * M.nrows * (size_t)M.ens_E;
+            MeasEnsArgs G{y, M.d_ens_acc, (long long *)(M.d_ens_acc + 4 * plane), M.d_ens_member, M.d_ens_off, len, pitch, s - M.pos,
+                          s - M.start, M.ens_stride, M.ens_E, 0, 0, M.ens_G, A.ny, M.nrows, {}};
+            meas_ensemble_range(G.m0, len, G.stride, &G.e0, &G.nrec);
+            memcpy(G.row, row, sizeof(G.row));
+            HIPCHK(meas_ensemble_launch(G, st));
+        }
     }
     M.pos += n;
     return ACME_OK;
@@ -2220,6 +2237,11 @@ static int meas_zero(acme_batch *b) {
         HIPCHK(meas_target_zero(M.d_tgt_acc, P * (size_t)MEAS_TARGET_SLOTS));
         HIPCHK(be::device_sync());
     }
+    if (M.ens) {        // every slot back to the start values (the groups and the stride stay)
+        const size_t plane = (size_t)M.ens_G * M.nrows * (size_t)M.ens_E;
+        HIPCHK(meas_ensemble_start(M.d_ens_acc, (long long *)(M.d_ens_acc + 4 * plane), plane));
+        HIPCHK(be::device_sync());
+    }
     if (M.wS) {         // the sections' states (the coefficients stay)
         HIPCHK(meas_weight_zero(M.d_wstate, P * 2 * (size_t)M.wS));
         HIPCHK(be::device_sync());
@@ -2397,6 +2419,7 @@ int acme_batch_set_measurement_series(acme_batch *b, long long win, long long ho
     if (M.spec) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a spectrum (a spectrum per window is not supported)");
     if (M.cross) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a cross-spectrum (a cross-spectrum per window is not supported)");
     if (M.target) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a target (a target per window is not supported)");
+    if (M.ens) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has an ensemble (an ensemble per window is not supported)");
     if (M.length != 0) return fail(ACME_ERR_INVALID, "measurement series: the armed measurement's length must be 0 (the series sets the windows)");
     if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement series: samples have been fed since arming (arm or reset the measurement first)");
     if (win < 1) return fail(ACME_ERR_INVALID, "measurement series: win must be >= 1");
@@ -2806,6 +2829,75 @@ int acme_batch_get_measurement_weighting(acme_batch *b, double *sos, int *S) {
     if (!M.on || !M.wS) return fail(ACME_ERR_INVALID, "no measurement weighting is set");
     if (S) *S = M.wS;
     if (sos) memcpy(sos, M.wsos, sizeof(M.wsos));
+    return ACME_OK;
+}
+
+int acme_batch_set_measurement_ensemble(acme_batch *b, const int *group, int G, long long stride) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    acme_batch::Measurement &M = b->meas;
+    if (!M.on) return fail(ACME_ERR_INVALID, "measurement ensemble: no measurement is armed");
+    if (M.W) return fail(ACME_ERR_UNSUPPORTED, "measurement ensemble: the measurement has a series of windows (an ensemble per window is not supported)");
+    if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement ensemble: samples have been fed since arming (arm or reset the measurement first)");
+    if (M.length <= 0) return fail(ACME_ERR_INVALID, "measurement ensemble: the armed measurement's window must be bounded (length > 0)");
+    if (G < 1) return fail(ACME_ERR_INVALID, "measurement ensemble: G must be >= 1");
+    if (stride < 1) return fail(ACME_ERR_INVALID, "measurement ensemble: stride must be >= 1");
+    const long long E = (M.length - 1) / stride + 1, GR = (long long)G * (long long)M.nrows;
+    if (GR > 0 && E > MEAS_MAX_ENSEMBLE / GR)
+        return fail(ACME_ERR_INVALID, "measurement ensemble: G nrows E exceeds " + std::to_string(MEAS_MAX_ENSEMBLE));
+    for (long long i = 0; group && i < b->N; ++i)
+        if (group[i] < -1 || group[i] >= G)
+            return fail(ACME_ERR_INVALID, "measurement ensemble: group of instance " + std::to_string(i) + " is outside -1 ... G - 1 = " + std::to_string(G - 1));
+    std::vector<int> member;
+    std::vector<long long> off;
+    meas_ensemble_plan(group, b->N, G, &member, &off);
+    const size_t plane = (size_t)GR * (size_t)E;
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    (void)be::dfree(M.d_ens_member); (void)be::dfree(M.d_ens_off); (void)be::dfree(M.d_ens_acc);
+    M.d_ens_member = nullptr;           // (an ensemble set again replaces the earlier one)
+    M.d_ens_off = nullptr;
+    M.d_ens_acc = nullptr;
+    M.ens = false;
+    HIPCHK(be::dmalloc((void **)&M.d_ens_member, sizeof(int) * std::max<size_t>(member.size(), 1)));
+    HIPCHK(be::dmalloc((void **)&M.d_ens_off, sizeof(long long) * off.size()));
+    HIPCHK(be::dmalloc((void **)&M.d_ens_acc, sizeof(double) * std::max<size_t>(6 * plane, 1)));
+    if (!member.empty()) HIPCHK(be::copy_h2d(M.d_ens_member, member.data(), sizeof(int) * member.size()));
+    HIPCHK(be::copy_h2d(M.d_ens_off, off.data(), sizeof(long long) * off.size()));
+    HIPCHK(meas_ensemble_start(M.d_ens_acc, (long long *)(M.d_ens_acc + 4 * plane), plane));
+    HIPCHK(be::device_sync());
+    M.ens_G = G;
+    M.ens_stride = stride;
+    M.ens_E = E;
+    M.ens_off = off;
+    M.ens = true;
+    return ACME_OK;
+}
+
+int acme_batch_get_measurement_ensemble(acme_batch *b, double *out, long long *arg, long long *members, long long *filled) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const acme_batch::Measurement &M = b->meas;
+    if (!M.on || !M.ens) return fail(ACME_ERR_INVALID, "no measurement ensemble is set");
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    const long long end = M.start + M.length;
+    const long long cnt = (M.pos < end ? M.pos : end) - M.start;
+    if (filled) *filled = cnt > 0 ? (cnt - 1) / M.ens_stride + 1 : 0;
+    for (int g = 0; members && g < M.ens_G; ++g) members[g] = M.ens_off[(size_t)g + 1] - M.ens_off[(size_t)g];
+    const size_t GR = (size_t)M.ens_G * M.nrows, E = (size_t)M.ens_E, plane = GR * E;
+    if (out) {
+        std::vector<double> a(4 * plane);
+        if (!a.empty()) HIPCHK(be::copy_d2h(a.data(), M.d_ens_acc, sizeof(double) * a.size()));
+        for (size_t q = 0; q < plane; ++q)
+            for (int k = 0; k < 4; ++k) out[q * 4 + k] = a[(size_t)k * plane + q];
+    }
+    if (arg) {
+        std::vector<long long> a(2 * plane);
+        if (!a.empty()) HIPCHK(be::copy_d2h(a.data(), M.d_ens_acc + 4 * plane, sizeof(long long) * a.size()));
+        for (size_t q = 0; q < plane; ++q)
+            for (int k = 0; k < 2; ++k) arg[q * 2 + k] = a[(size_t)k * plane + q];
+    }
     return ACME_OK;
 }
 

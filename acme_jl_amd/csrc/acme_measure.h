@@ -95,6 +95,19 @@
 // moments unit's tiles, four waves staging jointly through two LDS buffers, the next tile's loads in flight while the first
 // wave walks the current tile's chains in place; the emulator walks meas_weight_chain.
 //
+// ENSEMBLE (acme_batch_set_measurement_ensemble): the one form that reduces over INSTANCES at one time sample -- the instances
+// in G groups, window sample m recorded iff m mod stride == 0 in slot e = m / stride; per group, measured row and slot six
+// values, each ONE chain over the group's members in ascending instance order, no fused multiply-add: S += v, Q += v v, the
+// minimum and the maximum with the index of the member that set them (meas_min / meas_max with the index carried).  A slot
+// is written exactly once, by the chunk that holds its sample; nothing carries.  The accumulators are plane-major,
+// [6][G nrows][E] (S, Q, min, max as doubles, imin, imax as long long).  The plan -- the members sorted by (group, instance)
+// and the groups' offsets [G + 1] -- is built on the host at arming.  One more kernel per chunk
+// (acme_meas_ensemble_kernel<SPLIT>): a lane per recorded slot of the chunk, walking its group's member list with sixteen
+// members' loads in flight ahead of the chains (at ny = 1, stride = 1 a wave's load is one member's 64 consecutive samples,
+// 512 contiguous bytes); a block is four waves -- four tiles of 64 slots with all chains each, or, where that leaves fewer
+// waves than the device has SIMDs, ONE tile with the four chains (S | Q | min | max) split over the waves; the emulator walks
+// meas_ensemble_chain.
+//
 // The per-element functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with g++).
 #pragma once
@@ -365,6 +378,92 @@ inline void meas_target_plan(const int *which, const long long *lag, long long n
             if (q - i * nrows != j0 || which[i] != which[i0] || lag[i] != lag[i0]) u = 0;
         }
         (*wuni)[(size_t)w] = u;
+    }
+}
+
+// ensemble: the chunk's first sample is number m0 >= 0 of the window; window sample m is recorded iff m mod stride == 0, in
+// slot e = m / stride.  acc is [4][G * nrows][E], the planes S, Q, min, max; arg is [2][G * nrows][E], the planes imin, imax
+constexpr long long MEAS_MAX_ENSEMBLE = 1ll << 24;  // G nrows E at most (the table cap of the sources and the target)
+constexpr int MEAS_ENS_WAVES = 4;           // waves per block: four tiles of slots, or one tile with the chains split (SPLIT)
+constexpr int MEAS_ENS_AHEAD = 16;          // members whose loads are in flight ahead of the chains
+constexpr long long MEAS_ENS_SPLIT_BELOW = 1024;    // SPLIT where the unsplit launch has fewer waves (256 CUs x 4 SIMDs)
+
+struct MeasEnsArgs {
+    const double *y;            // instance i, sample t, row r at y[(i * pitch + t0 + t) * ny + r]
+    double *acc;                // [4][G * nrows][E]
+    long long *arg;             // [2][G * nrows][E]
+    const int *member;          // the instances that are in a group, sorted by (group, instance)
+    const long long *off;       // [G + 1]: group g's members are member[off[g]] ... member[off[g + 1] - 1]
+    long long len, pitch, t0, m0, stride, E;
+    long long e0, nrec;         // the chunk's recorded slots e0 ... e0 + nrec - 1 (meas_ensemble_range)
+    int G, ny, nrows;
+    unsigned char row[64];      // the measured rows, ascending
+};
+
+// the slots whose samples lie in the chunk [m0, m0 + len): e0 = ceil(m0 / stride), and as many as fit
+ACME_HD inline void meas_ensemble_range(long long m0, long long len, long long stride, long long *e0, long long *nrec) {
+    *e0 = (m0 + stride - 1) / stride;
+    const long long last = (m0 + len - 1) / stride;         // (len >= 1)
+    *nrec = last >= *e0 ? last - *e0 + 1 : 0;
+}
+
+// the four chains' steps, shared by every backend: each rounded on its own, the extremes with the member's index carried
+ACME_HD ACME_NO_CONTRACT_FN inline void meas_ens_sum(double &S, double v) {
+    ACME_NO_CONTRACT
+    S = S + v;
+}
+ACME_HD ACME_NO_CONTRACT_FN inline void meas_ens_sq(double &Q, double v) {
+    ACME_NO_CONTRACT
+    const double q = v * v;
+    Q = Q + q;
+}
+ACME_HD inline void meas_ens_min(double &mn, long long &imin, double v, long long i) {
+    if (v < mn || v != v) { mn = v; imin = i; }
+}
+ACME_HD inline void meas_ens_max(double &mx, long long &imax, double v, long long i) {
+    if (v > mx || v != v) { mx = v; imax = i; }
+}
+
+// one (group, row) pair gr = g * nrows + j and one recorded slot e of the chunk, member after member: the contract of
+// include/acme_hip.h as a plain loop (the reference order every backend keeps)
+ACME_HD inline void meas_ensemble_chain(const MeasEnsArgs &A, long long gr, long long e) {
+    const long long GR = (long long)A.G * A.nrows, g = gr / A.nrows, j = gr - g * A.nrows;
+    const double *yp = A.y + (A.t0 + (e * A.stride - A.m0)) * A.ny + A.row[j];
+    double S = 0.0, Q = 0.0, mn = INFINITY, mx = -INFINITY;
+    long long imin = -1, imax = -1;
+    for (long long k = A.off[g]; k < A.off[g + 1]; ++k) {
+        const long long i = A.member[k];
+        const double v = yp[i * A.pitch * A.ny];
+        meas_ens_sum(S, v);
+        meas_ens_sq(Q, v);
+        meas_ens_min(mn, imin, v, i);
+        meas_ens_max(mx, imax, v, i);
+    }
+    const long long at = gr * A.E + e, plane = GR * A.E;
+    A.acc[at] = S; A.acc[plane + at] = Q; A.acc[2 * plane + at] = mn; A.acc[3 * plane + at] = mx;
+    A.arg[at] = imin; A.arg[plane + at] = imax;
+}
+
+// the start values of one element of the planes: S, Q 0.0; min +inf; max -inf; imin, imax -1
+ACME_HD inline void meas_ens_start(double *acc, long long *arg, long long plane, long long at) {
+    acc[at] = 0.0; acc[plane + at] = 0.0; acc[2 * plane + at] = INFINITY; acc[3 * plane + at] = -INFINITY;
+    arg[at] = -1; arg[plane + at] = -1;
+}
+
+// the ensemble's plan: the members sorted by (group, instance) and the groups' offsets; group NULL: all in group 0
+template <class VI, class VL>
+inline void meas_ensemble_plan(const int *group, long long n, int G, VI *member, VL *off) {
+    off->assign((size_t)G + 1, 0);
+    for (long long i = 0; i < n; ++i) {
+        const int g = group ? group[i] : 0;
+        if (g >= 0) ++(*off)[(size_t)g + 1];
+    }
+    for (int g = 0; g < G; ++g) (*off)[(size_t)g + 1] += (*off)[(size_t)g];
+    member->assign((size_t)(*off)[(size_t)G], 0);
+    std::vector<long long> at(off->begin(), off->end() - 1);
+    for (long long i = 0; i < n; ++i) {     // (ascending i: every group's members in ascending instance order)
+        const int g = group ? group[i] : 0;
+        if (g >= 0) (*member)[(size_t)at[(size_t)g]++] = (int)i;
     }
 }
 
@@ -1350,7 +1449,94 @@ __global__ __launch_bounds__(64 * acme::MEAS_WEIGHT_WAVES) void acme_meas_weight
         for (int k = 0; k < S; ++k) { A.state[2 * k * Pn + p] = s1[k]; A.state[(2 * k + 1) * Pn + p] = s2[k]; }
     }
 }
+
+// ensemble: a lane per recorded slot of the chunk, walking the member list of its (group, row) pair in order -- the list's
+// entries are wave-uniform (scalar loads), a member's load is the lanes' samples of that instance (at ny = 1 and stride = 1
+// 64 consecutive doubles), MEAS_ENS_AHEAD members' loads are issued before the first of their chain steps.  ROLE 0 ... 3: the
+// one chain S | Q | min | max (SPLIT: the four waves of a block share a tile of 64 slots); ROLE 4: all four (the four
+// waves of a block take four tiles).  No LDS, no barrier: a lane without a slot leaves at once.  The values and the order of
+// every chain are meas_ensemble_chain's.
+template <int ROLE>
+__device__ inline void acme_meas_ens_step(double v, long long i, double &S, double &Q, double &mn, double &mx, long long &imin,
+                                          long long &imax) {
+    using namespace acme;
+    if (ROLE == 0 || ROLE == 4) meas_ens_sum(S, v);
+    if (ROLE == 1 || ROLE == 4) meas_ens_sq(Q, v);
+    if (ROLE == 2 || ROLE == 4) meas_ens_min(mn, imin, v, i);
+    if (ROLE == 3 || ROLE == 4) meas_ens_max(mx, imax, v, i);
+}
+template <int ROLE>
+__device__ inline void acme_meas_ens_walk(const acme::MeasEnsArgs &A, long long gr, long long e) {
+    using namespace acme;
+    const long long GR = (long long)A.G * A.nrows, g = gr / A.nrows, j = gr - g * A.nrows;
+    const double *yp = A.y + (A.t0 + (e * A.stride - A.m0)) * A.ny + A.row[j];
+    const long long ipitch = A.pitch * A.ny, k1 = A.off[g + 1];
+    double S = 0.0, Q = 0.0, mn = INFINITY, mx = -INFINITY;
+    long long imin = -1, imax = -1, k = A.off[g];
+    for (; k + MEAS_ENS_AHEAD <= k1; k += MEAS_ENS_AHEAD) {
+        int id[MEAS_ENS_AHEAD];
+        double v[MEAS_ENS_AHEAD];
+#pragma unroll
+        for (int q = 0; q < MEAS_ENS_AHEAD; ++q) {      // the loads are in flight together
+            id[q] = A.member[k + q];
+            v[q] = yp[(long long)id[q] * ipitch];
+        }
+#pragma unroll
+        for (int q = 0; q < MEAS_ENS_AHEAD; ++q) acme_meas_ens_step<ROLE>(v[q], id[q], S, Q, mn, mx, imin, imax);
+    }
+    for (; k < k1; ++k) {
+        const long long i = A.member[k];
+        acme_meas_ens_step<ROLE>(yp[i * ipitch], i, S, Q, mn, mx, imin, imax);
+    }
+    const long long at = gr * A.E + e, plane = GR * A.E;
+    if (ROLE == 0 || ROLE == 4) A.acc[at] = S;
+    if (ROLE == 1 || ROLE == 4) A.acc[plane + at] = Q;
+    if (ROLE == 2 || ROLE == 4) { A.acc[2 * plane + at] = mn; A.arg[at] = imin; }
+    if (ROLE == 3 || ROLE == 4) { A.acc[3 * plane + at] = mx; A.arg[plane + at] = imax; }
+}
+// grid: (group, row) pairs x the blocks of a pair's slots -- tiles of 64 (SPLIT) or of 64 * MEAS_ENS_WAVES slots
+template <bool SPLIT>
+__global__ __launch_bounds__(64 * acme::MEAS_ENS_WAVES) void acme_meas_ensemble_kernel(acme::MeasEnsArgs A) {
+    using namespace acme;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long per = SPLIT ? 64 : 64 * MEAS_ENS_WAVES, blocks = (A.nrec + per - 1) / per;
+    const long long gr = (long long)blockIdx.x / blocks, tb = (long long)blockIdx.x - gr * blocks;
+    const long long q = tb * per + (SPLIT ? 0 : 64 * wave) + lane;     // the lane's slot of the chunk
+    if (q >= A.nrec) return;
+    const long long e = A.e0 + q;
+    if (!SPLIT) acme_meas_ens_walk<4>(A, gr, e);
+    else if (wave == 0) acme_meas_ens_walk<0>(A, gr, e);
+    else if (wave == 1) acme_meas_ens_walk<1>(A, gr, e);
+    else if (wave == 2) acme_meas_ens_walk<2>(A, gr, e);
+    else acme_meas_ens_walk<3>(A, gr, e);
+}
+__global__ __launch_bounds__(256) void acme_meas_ens_start_kernel(double *acc, long long *arg, long long plane) {
+    const long long at = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (at < plane) acme::meas_ens_start(acc, arg, plane, at);
+}
 namespace acme {
+// SPLIT where the unsplit launch would leave SIMDs without a wave; ACME_ENS_SPLIT=0 / 1 in the environment forces one (A/B
+// measurements, tests)
+inline bool meas_ens_split(long long pairs, long long nrec) {
+    if (const char *e = getenv("ACME_ENS_SPLIT")) { if (e[0] == '0') return false; if (e[0] == '1') return true; }
+    return pairs * ((nrec + 63) / 64) < MEAS_ENS_SPLIT_BELOW;
+}
+inline int meas_ensemble_launch(const MeasEnsArgs &A, hipStream_t st) {
+    const long long pairs = (long long)A.G * A.nrows;
+    if (pairs <= 0 || A.nrec <= 0) return 0;
+    if (meas_ens_split(pairs, A.nrec))
+        hipLaunchKernelGGL(acme_meas_ensemble_kernel<true>, dim3((unsigned)(pairs * ((A.nrec + 63) / 64))), dim3(64 * MEAS_ENS_WAVES), 0, st, A);
+    else
+        hipLaunchKernelGGL(acme_meas_ensemble_kernel<false>, dim3((unsigned)(pairs * ((A.nrec + 64 * MEAS_ENS_WAVES - 1) / (64 * MEAS_ENS_WAVES)))),
+                           dim3(64 * MEAS_ENS_WAVES), 0, st, A);
+    return (int)hipGetLastError();
+}
+// every slot back to the start values (plane = G nrows E elements)
+inline int meas_ensemble_start(double *acc, long long *arg, size_t plane) {
+    if (plane == 0) return 0;
+    hipLaunchKernelGGL(acme_meas_ens_start_kernel, dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, 0, acc, arg, (long long)plane);
+    return (int)hipGetLastError();
+}
 template <int S>
 inline int meas_weight_launch_s(const MeasWeightArgs &A, hipStream_t st) {
     hipLaunchKernelGGL(acme_meas_weight_kernel<S>, dim3((unsigned)((A.n * A.nrows + 63) / 64)), dim3(64 * MEAS_WEIGHT_WAVES), 0, st, A);
@@ -1596,6 +1782,15 @@ inline int meas_target_launch(const MeasTargetArgs &A, void *) {
 }
 inline int meas_target_zero(double *p, size_t count) {
     std::fill(p, p + count, 0.0);
+    return 0;
+}
+inline int meas_ensemble_launch(const MeasEnsArgs &A, void *) {
+    for (long long gr = 0; gr < (long long)A.G * A.nrows; ++gr)
+        for (long long e = A.e0; e < A.e0 + A.nrec; ++e) meas_ensemble_chain(A, gr, e);
+    return 0;
+}
+inline int meas_ensemble_start(double *acc, long long *arg, size_t plane) {
+    for (size_t at = 0; at < plane; ++at) meas_ens_start(acc, arg, (long long)plane, (long long)at);
     return 0;
 }
 inline int meas_fold_launch(const MeasFoldArgs &A, void *) {

@@ -73,6 +73,7 @@ ABI_SYMBOLS = [
     "acme_batch_get_measurement_cross_table",
     "acme_batch_set_measurement_target", "acme_batch_get_measurement_target",
     "acme_batch_set_measurement_weighting", "acme_batch_get_measurement_weighting",
+    "acme_batch_set_measurement_ensemble", "acme_batch_get_measurement_ensemble",
 ]
 
 SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE, SOURCE_NOISE = 1, 2, 3, 4, 5
@@ -81,6 +82,7 @@ MAX_SOURCE_TONES = 4
 MAX_FOLD_PERIOD = 65536
 MAX_TARGETS = 64
 MAX_WEIGHTING_SECTIONS = 8
+MAX_ENSEMBLE = 16777216
 _SOURCE_KINDS = {"const": SOURCE_CONST, "sine": SOURCE_SINE, "table": SOURCE_TABLE, "multisine": SOURCE_MULTISINE, "noise": SOURCE_NOISE,
                  SOURCE_CONST: SOURCE_CONST, SOURCE_SINE: SOURCE_SINE, SOURCE_TABLE: SOURCE_TABLE, SOURCE_MULTISINE: SOURCE_MULTISINE,
                  SOURCE_NOISE: SOURCE_NOISE}
@@ -215,6 +217,8 @@ class Library:
         L.acme_batch_get_measurement_cross_table.argtypes = [vp, dp, dp]
         L.acme_batch_set_measurement_target.argtypes = [vp, dp, C.c_longlong, C.c_longlong, ip, lp, C.c_double]
         L.acme_batch_get_measurement_target.argtypes = [vp, dp, lp]
+        L.acme_batch_set_measurement_ensemble.argtypes = [vp, ip, C.c_int, C.c_longlong]
+        L.acme_batch_get_measurement_ensemble.argtypes = [vp, dp, lp, lp, lp]
         L.acme_batch_set_measurement_weighting.argtypes = [vp, dp, C.c_int]
         L.acme_batch_get_measurement_weighting.argtypes = [vp, dp, C.POINTER(C.c_int)]
 
@@ -569,6 +573,66 @@ class MeasurementTarget:
         return cls(np.concatenate([p.sums for p in parts]), a.count, a.rows, ym)
 
 
+class MeasurementEnsemble:
+    """What ``ModelRunner.measurement_ensemble()`` returns: the statistics ACROSS the instances of each group at every
+    recorded sample of the window.  ``sum``, ``sumsq``, ``min``, ``max`` (G, nrows, E): the chains themselves, undivided --
+    slot e is window sample ``e * stride``; ``argmin``, ``argmax`` (G, nrows, E): the instance that set the extreme (-1: no
+    member); ``members`` (G,): the groups' sizes; ``filled``: the slots recorded so far (the others, and every slot of an
+    empty group, read 0.0, 0.0, +inf, -inf, -1, -1); ``rows`` the measured output rows."""
+
+    def __init__(self, sum, sumsq, min, max, argmin, argmax, members, filled, stride, rows):
+        self.sum, self.sumsq, self.min, self.max, self.argmin, self.argmax = sum, sumsq, min, max, argmin, argmax
+        self.members, self.filled, self.stride, self.rows = np.asarray(members, dtype=np.int64), int(filled), int(stride), tuple(rows)
+
+    def mean(self):
+        """the ensemble average ``sum / members`` (G, nrows, E); NaN for an empty group"""
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return self.sum / self.members[:, None, None]
+
+    def std(self, ddof=0):
+        """the standard deviation across a group's members, from ``sumsq`` and ``sum`` (G, nrows, E); a difference that
+        rounding takes below zero reads 0.0"""
+        n = self.members[:, None, None].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            var = (self.sumsq - self.sum * self.sum / n) / (n - ddof)
+            return np.sqrt(np.where(var < 0.0, 0.0, var))
+
+    def band(self, sigmas=None):
+        """(lower, upper), (G, nrows, E) each: the min / max envelope -- every member's waveform lies inside --, or with
+        ``sigmas=k`` the band ``mean -+ k std``"""
+        if sigmas is None:
+            return self.min, self.max
+        m, s = self.mean(), self.std()
+        return m - sigmas * s, m + sigmas * s
+
+    def trace(self, g):
+        """the waveform (nrows, E) of the one member of group ``g``, as the run produced it (-0.0 reads +0.0)"""
+        if self.members[g] != 1:
+            raise ValueError(f"group {g} has {int(self.members[g])} members: a trace is the waveform of a one-member group")
+        return self.sum[g]
+
+    @classmethod
+    def join(cls, parts, offsets):
+        """the shards' results joined by group: every group's members lie in ONE shard (the others hold its start values);
+        ``offsets``: the shards' first instances, added to their indices"""
+        a = parts[0]
+        if any((p.filled, p.stride, p.rows, p.sum.shape) != (a.filled, a.stride, a.rows, a.sum.shape) for p in parts):
+            raise ValueError("the shards' ensembles differ in their slots, strides or measured rows")
+        out = [np.array(getattr(a, k)) for k in ("sum", "sumsq", "min", "max", "argmin", "argmax")]
+        members = np.zeros_like(a.members)
+        for p, lo in zip(parts, offsets):
+            has = p.members > 0
+            if (members[has] > 0).any():
+                raise ValueError(f"group {int(np.flatnonzero(has & (members > 0))[0])} has members in more than one shard")
+            members[has] = p.members[has]
+            for o, k in zip(out, ("sum", "sumsq", "min", "max")):
+                o[has] = getattr(p, k)[has]
+            for o, k in zip(out[4:], ("argmin", "argmax")):
+                idx = getattr(p, k)[has]
+                o[has] = np.where(idx >= 0, idx + lo, idx)
+        return cls(*out, members, a.filled, a.stride, a.rows)
+
+
 class MeasurementWeighting:
     """What ``ModelRunner.measurement_weighting()`` returns, and what ``set_measurement_weighting`` accepts: a cascade of
     second-order sections, ``sos`` (S, 5) with the rows ``b0 b1 b2 a1 a2`` of
@@ -813,6 +877,8 @@ class ModelRunner:
         self._cross = None              # (nfft, hop, in_row) of the cross-spectrum set on the armed measurement
         self._target = False            # a target is set on the armed measurement
         self._weighting = False         # a weighting is set on the armed measurement
+        self._ensemble = None           # (G, stride, E) of the ensemble set on the armed measurement
+        self._length = 0                # the armed measurement's window length (0: unbounded)
         self._sources = {}              # input row -> kind, while the row has a source
         self._sine = {}                 # input row -> (f_den, f_num as armed) of its sine source
         self._progress_cb = None
@@ -902,12 +968,14 @@ class ModelRunner:
             self.lib.check(self.lib.L.acme_batch_set_measurement_per_instance(self.h, spec[0], spec[1], int(f_den), fp,
                                                                               spec[4], spec[5]))
         self._meas = (int(harmonics), rows)
+        self._length = int(length)
         self._series = (int(start), None)
         self._fold = False
         self._spectrum = None
         self._cross = None
         self._target = False
         self._weighting = False
+        self._ensemble = None
         return self
 
     def set_measurement_bins(self, coef, start=0, length=0, rows=None, f_den=None, f_num=None, tones_from_source=None):
@@ -941,12 +1009,14 @@ class ModelRunner:
         self.lib.check(self.lib.L.acme_batch_set_measurement_bins(self.h, spec[0], spec[1], int(f_den), tones, fp, ca.shape[0],
                                                                   _ip(ca), spec[5]))
         self._meas = (ca.shape[0], rows)
+        self._length = int(length)
         self._series = (int(start), None)
         self._fold = False
         self._spectrum = None
         self._cross = None
         self._target = False
         self._weighting = False
+        self._ensemble = None
         return self
 
     def measurement_plan(self):
@@ -972,6 +1042,7 @@ class ModelRunner:
         self._cross = None
         self._target = False
         self._weighting = False
+        self._ensemble = None
         return self
 
     def set_measurement_series(self, win, hop=None, windows=1):
@@ -1192,6 +1263,44 @@ class ModelRunner:
         out, S = np.zeros((MAX_WEIGHTING_SECTIONS, 5)), C.c_int(0)
         self.lib.check(self.lib.L.acme_batch_get_measurement_weighting(self.h, _dp(out), C.byref(S)))
         return MeasurementWeighting(out[:S.value].copy())
+
+    def set_measurement_ensemble(self, groups=None, n_groups=None, stride=1):
+        """Reduce the armed measurement's window ACROSS the instances (``acme_batch_set_measurement_ensemble``): per group,
+        measured row and recorded sample the sum, the sum of squares, the minimum and the maximum over the group's members
+        and the instances that set the extremes -- the band of a Monte-Carlo batch with no y stored.  ``groups``: N integers,
+        instance i's group 0 ... G - 1 or -1 (in none); None: every instance in group 0.  ``n_groups``: G (None: the
+        largest group index + 1).  ``stride``: every ``stride``-th window sample is recorded.  Needs an armed measurement
+        with a bounded window (``length > 0``) that has not been fed yet; not together with a series;
+        ``measurement_ensemble`` reads it."""
+        if self._meas is None:
+            raise AcmeError("no measurement is armed")
+        ga = None
+        if groups is not None:
+            if np.shape(groups) != (self.n,):
+                raise DimensionMismatch(f"groups needs {self.n} values")
+            ga = np.ascontiguousarray(groups, dtype=np.int32)
+            if not np.all(ga == np.asarray(groups)):
+                raise DimensionMismatch("groups must be integers")
+        G = int(n_groups) if n_groups is not None else 1 if ga is None else max(int(ga.max(initial=-1)) + 1, 1)
+        stride = int(stride)
+        self.lib.check(self.lib.L.acme_batch_set_measurement_ensemble(self.h, None if ga is None else _ip(ga), G, stride))
+        self._ensemble = (G, stride, (self._length - 1) // stride + 1)
+        return self
+
+    def measurement_ensemble(self):
+        """the statistics across the groups' instances so far (``acme_batch_get_measurement_ensemble``): a
+        ``MeasurementEnsemble``"""
+        if self._meas is None or self._ensemble is None:
+            raise AcmeError("no measurement ensemble is set")
+        rows = self._meas[1]
+        G, stride, E = self._ensemble
+        out, arg = np.empty((G, len(rows), E, 4)), np.empty((G, len(rows), E, 2), dtype=np.int64)
+        members, filled = np.zeros(G, dtype=np.int64), C.c_longlong(0)
+        lp = C.POINTER(C.c_longlong)
+        self.lib.check(self.lib.L.acme_batch_get_measurement_ensemble(self.h, _dp(out), arg.ctypes.data_as(lp),
+                                                                      members.ctypes.data_as(lp), C.byref(filled)))
+        return MeasurementEnsemble(*(out[..., k].copy() for k in range(4)), arg[..., 0].copy(), arg[..., 1].copy(), members,
+                                   filled.value, stride, rows)
 
     def reset_measurement(self):
         """zero the accumulators and restart the window's clock (``acme_batch_reset_measurement``)"""
@@ -1883,6 +1992,30 @@ class MultiDeviceRunner:
     def measurement_target(self, raw=False):
         """the shards' ``MeasurementTarget`` results, concatenated along the instances (``raw`` as ``ModelRunner``'s)"""
         return MeasurementTarget.concatenate([r.measurement_target(raw) for r in self.runners if r is not None])
+
+    def set_measurement_ensemble(self, groups=None, n_groups=None, stride=1):
+        """``ModelRunner.set_measurement_ensemble`` on every device's batch, ``groups`` sliced over the devices.  Every group
+        must lie wholly in one device's range of instances: a chain over shards would not be the chain over one device
+        (``ValueError`` naming the group otherwise)."""
+        ga = np.zeros(self.n, dtype=np.int64) if groups is None else np.asarray(groups)
+        if ga.shape != (self.n,):
+            raise DimensionMismatch(f"groups needs {self.n} values")
+        G = int(n_groups) if n_groups is not None else max(int(ga.max(initial=-1)) + 1, 1)
+        owner = {}
+        for k, (lo, hi) in enumerate(self.ranges):
+            for g in np.unique(ga[lo:hi]):
+                if g >= 0 and owner.setdefault(int(g), k) != k:
+                    raise ValueError(f"group {int(g)} has members on more than one device (shards {owner[int(g)]} and {k}): "
+                                     "an ensemble's chains do not cross devices")
+        for r, (lo, hi) in zip(self.runners, self.ranges):
+            if r is not None:
+                r.set_measurement_ensemble(ga[lo:hi], G, stride)
+        return self
+
+    def measurement_ensemble(self):
+        """the shards' ``MeasurementEnsemble`` results joined by group, the indices those of the whole batch"""
+        live = [(r, lo) for r, (lo, hi) in zip(self.runners, self.ranges) if r is not None]
+        return MeasurementEnsemble.join([r.measurement_ensemble() for r, _ in live], [lo for _, lo in live])
 
     def set_measurement_weighting(self, sos):
         """``ModelRunner.set_measurement_weighting`` on every device's batch: the same cascade everywhere"""

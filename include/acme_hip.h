@@ -542,6 +542,49 @@ int acme_batch_set_measurement_weighting(acme_batch *b, const double *sos /* hos
 /* the cascade as set: sos[8][5] (may be NULL; the rows from S on are 0.0) and *S (may be NULL).  ACME_ERR_INVALID without a
  * weighting. */
 int acme_batch_get_measurement_weighting(acme_batch *b, double *sos /* [8][5] or NULL */, int *S);
+/* An ENSEMBLE of the window: the armed measurement (any of the three forms with a BOUNDED window, length > 0, no sample fed
+ * since arming or the last reset) also reduces over the INSTANCES at one time sample, where every other form reduces over
+ * time for one instance -- the band of the output waveform over the draws of a Monte-Carlo batch (mean, +- sigma, min / max
+ * envelope), which draw is the worst case at each point of the period, the same per cell of a grid with M draws a cell, the
+ * ensemble average of a batch in which every instance hears its own noise row; with groups of one member, the waveform of a
+ * few chosen instances of a y = NULL run.  6 values per group, measured row and recorded sample in place of y [N][T][ny].
+ *   group    HOST array [N] or NULL (every instance in group 0); group[i] in 0 ... G - 1: the group of instance i, -1: in no
+ *            group.  Groups are arbitrary (interleaved, not contiguous, of unequal size); a group may be empty.
+ *   G        the number of groups, >= 1
+ *   stride   >= 1: window sample m = n - start is recorded iff m mod stride == 0, in slot e = m / stride;
+ *            E = ceil(length / stride) slots; G nrows E <= ACME_MAX_ENSEMBLE.
+ * Arithmetic, per group g, j-th measured row and slot e: six values, each ONE chain over the group's members in ASCENDING
+ * INSTANCE ORDER i, every product and every sum rounded on its own, NO fused multiply-add; v is the value the other forms see
+ * (the weighted row behind a weighting, the base-rate row after the decimation of an oversampled batch):
+ *   S = S + v                                    from 0.0
+ *   q = v v;  Q = Q + q                          from 0.0
+ *   if (v < mn || v != v) { mn = v; imin = i; }  from +inf and -1
+ *   if (v > mx || v != v) { mx = v; imax = i; }  from -inf and -1
+ * -- the measurement's min and max with the index carried: the FIRST member that attains an extreme keeps it; a NaN sticks in
+ * all four values of its (group, row, slot), and imin == imax name the NaN member (with several NaN members at one sample, the
+ * last of them, as the rule reads).  A group of ONE member therefore returns S = 0.0 + y: the stored y bit for bit, except
+ * that -0.0 reads +0.0 (min and max keep the sign).  A slot is written exactly once, by the chunk that holds its sample;
+ * nothing carries across chunks, slices or calls.  Slots not reached yet and empty groups read the start values.  The
+ * result depends on nothing but the run's samples: chunk, slice and call boundaries, host or device memory, the entry point,
+ * the oversampling factor and whether y is stored change none of its bits.  The measurement's own accumulators, plan,
+ * launches and getter are what they are without an ensemble; it takes one more kernel per chunk of the window, the member
+ * list and 6 x 8 bytes per (group, row, slot) of device memory.  A fold, a spectrum, a cross-spectrum, a target, a weighting
+ * and an ensemble may all be set together.
+ * ACME_ERR_INVALID (the message names the argument, and the instance of an entry of group): no measurement armed, samples
+ * already fed, an unbounded window (length == 0), G < 1, stride < 1, G nrows E beyond the cap, a group[i] outside -1 ... G - 1.
+ * ACME_ERR_UNSUPPORTED together with a series, whichever is set first.  Setting an ensemble again replaces the earlier one.
+ * _reset_measurement returns every slot to the start values and keeps group, G and stride; arming any form or
+ * _clear_measurement removes the ensemble; acme_batch_set_matrices carries it with the accumulators.  A batch without an
+ * ensemble launches, allocates and synchronises what it always did. */
+#define ACME_MAX_ENSEMBLE 16777216
+int acme_batch_set_measurement_ensemble(acme_batch *b, const int *group /* host [N]: 0 ... G - 1, -1: in no group; NULL: all in group 0 */,
+                                        int G, long long stride);
+/* the chains so far, undivided (each may be NULL): out[G][nrows][E][4] in the order S, Q, min, max; arg[G][nrows][E][2] the
+ * instances imin, imax (-1: no member); members[G] the groups' sizes; *filled the number of slots recorded so far,
+ * ceil(samples measured / stride).  ACME_ERR_INVALID without an ensemble.  Joins a pending acme_batch_run_async and
+ * synchronises the device. */
+int acme_batch_get_measurement_ensemble(acme_batch *b, double *out /* [G][nrows][E][4] */, long long *arg /* [G][nrows][E][2] */,
+                                        long long *members /* [G] */, long long *filled);
 /* switch the measurement off (y = NULL is refused again) */
 int acme_batch_clear_measurement(acme_batch *b);
 /* zero the accumulators and restart the window's clock (the armed parameters stay) */

@@ -40,7 +40,7 @@ export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host
        set_source_multisine!, set_source_noise!, set_measurement_bins!, set_measurement_series!, measurement_series,
        set_measurement_fold!, measurement_fold, set_measurement_spectrum!, measurement_spectrum,
        set_measurement_cross!, measurement_cross, set_measurement_target!, measurement_target,
-       set_measurement_weighting!, measurement_weighting
+       set_measurement_weighting!, measurement_weighting, set_measurement_ensemble!, measurement_ensemble
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
 
@@ -57,6 +57,7 @@ const ACME_MIN_SPECTRUM = 64
 const ACME_MAX_SPECTRUM = 4096
 const ACME_MAX_TARGETS = 64
 const ACME_MAX_WEIGHTING_SECTIONS = 8
+const ACME_MAX_ENSEMBLE = 16777216
 const ACME_SOURCE_CONST, ACME_SOURCE_SINE, ACME_SOURCE_TABLE, ACME_SOURCE_MULTISINE = Cint(1), Cint(2), Cint(3), Cint(4)
 const ACME_SOURCE_NOISE = Cint(5)
 const ACME_NOISE_UNIFORM, ACME_NOISE_GAUSSIAN = Cint(0), Cint(1)
@@ -226,6 +227,7 @@ mutable struct BatchRunner
     sources::Set{Int}                 # the input rows (1-based) that have a source
     spectrum::Int                     # nfft of the spectrum set on the armed measurement (0: none)
     cross::Int                        # nfft of the cross-spectrum set on the armed measurement (0: none)
+    ensemble::Tuple{Int,Int}          # (G, stride) of the ensemble set on the armed measurement ((0, 0): none)
 end
 
 # @showprogress of run!(runner, y, u) (src/ACME.jl:587-604,653): the library reports after every time slice of a
@@ -244,7 +246,7 @@ function BatchRunner(model::DiscreteModel, n::Integer; device::Integer=-1,
     b = Ref{Ptr{Cvoid}}()
     check(ccall((:acme_batch_create, lib), Cint, (Ptr{Cvoid}, Clonglong, Ref{AcmeOptions}, Ref{Ptr{Cvoid}}),
                 mh.h, n, opts, b))
-    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress, nothing, Set{Int}(), 0, 0)
+    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress, nothing, Set{Int}(), 0, 0, (0, 0))
     finalizer(r -> ccall((:acme_batch_destroy, lib), Cvoid, (Ptr{Cvoid},), r.h), r)
     if showprogress
         cb = @cfunction(progress_trampoline, Cvoid, (Ptr{Cvoid}, Clonglong, Clonglong))
@@ -488,6 +490,7 @@ function set_measurement!(r::BatchRunner, spec::MeasureSpec)
     r.meas = spec
     r.spectrum = 0
     r.cross = 0
+    r.ensemble = (0, 0)
     return r
 end
 function set_measurement!(r::BatchRunner; f_den=nothing, f_num=nothing, kwargs...)
@@ -512,6 +515,7 @@ function set_measurement!(r::BatchRunner, spec::MeasureSpec, f_den::Int64, f_num
     r.meas = spec
     r.spectrum = 0
     r.cross = 0
+    r.ensemble = (0, 0)
     return r
 end
 
@@ -537,6 +541,7 @@ function set_measurement_bins!(r::BatchRunner, coef::Matrix{<:Integer}, f_den::I
     r.meas = spec
     r.spectrum = 0
     r.cross = 0
+    r.ensemble = (0, 0)
     return r
 end
 
@@ -564,6 +569,7 @@ function clear_measurement!(r::BatchRunner)
     r.meas = nothing
     r.spectrum = 0
     r.cross = 0
+    r.ensemble = (0, 0)
     return r
 end
 
@@ -836,6 +842,51 @@ function measurement_weighting(r::BatchRunner)
     out = zeros(Float64, 5, ACME_MAX_WEIGHTING_SECTIONS)             # the ABI's [8][5]
     check(ccall((:acme_batch_get_measurement_weighting, lib), Cint, (Ptr{Cvoid}, Ptr{Cdouble}, Ref{Cint}), r.h, out, S))
     return Matrix{Float64}(transpose(out[:, 1:S[]]))
+end
+
+"""
+    set_measurement_ensemble!(runner; groups=nothing, n_groups=nothing, stride=1)
+
+Reduce the armed measurement's window ACROSS the instances (`acme_batch_set_measurement_ensemble`): per group, measured row
+and recorded sample the sum, the sum of squares, the minimum and the maximum over the group's members, in ascending instance
+order, and the instances that set the extremes.  `groups::Vector` (0-based, one per instance, `-1`: in no group; `nothing`:
+every instance in group 0), `n_groups` the number of groups (`nothing`: the largest index + 1), every `stride`-th window
+sample recorded.  Needs an armed measurement with a bounded window (`length > 0`) that has not been fed yet; not together
+with a series.
+"""
+function set_measurement_ensemble!(r::BatchRunner; groups=nothing, n_groups=nothing, stride::Integer=1)
+    r.meas === nothing && error("no measurement is armed")
+    g = perinstance(Cint, groups, r.n)
+    G = n_groups === nothing ? max(isempty(g) ? 1 : Int(maximum(g)) + 1, 1) : Int(n_groups)
+    GC.@preserve g check(ccall((:acme_batch_set_measurement_ensemble, lib), Cint, (Ptr{Cvoid}, Ptr{Cint}, Cint, Clonglong),
+                               r.h, ptr_or_null(g), G, stride))
+    r.ensemble = (G, Int(stride))
+    return r
+end
+
+"""
+    measurement_ensemble(runner) -> (sum, sumsq, min, max, argmin, argmax, members, filled)
+
+The statistics across the groups' instances so far (`acme_batch_get_measurement_ensemble`), for the groups and the stride
+that `set_measurement_ensemble!` set (the runner keeps both and sizes the arrays from them): the four chains, undivided,
+and the 0-based instances that set the extremes (`-1`: no member), `E x nrows x G` each with `E = cld(length, stride)`;
+`members` the groups' sizes; `filled` the number of slots recorded so far.
+"""
+function measurement_ensemble(r::BatchRunner)
+    spec = r.meas
+    n_groups, stride = r.ensemble
+    (spec === nothing || n_groups == 0) && error("no measurement ensemble is set")
+    ny = ACME.ny(r.model)
+    nrows = spec.rows == 0 ? min(ny, 64) : count_ones(spec.rows)
+    E = cld(spec.length, stride)
+    out = Array{Float64,4}(undef, 4, E, nrows, n_groups)             # the ABI's [G][nrows][E][4]
+    arg = Array{Int64,4}(undef, 2, E, nrows, n_groups)               # ... and [G][nrows][E][2]
+    members = zeros(Int64, n_groups)
+    filled = Ref{Clonglong}(0)
+    check(ccall((:acme_batch_get_measurement_ensemble, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Clonglong}, Ptr{Clonglong}, Ref{Clonglong}), r.h, out, arg, members, filled))
+    return (sum=out[1, :, :, :], sumsq=out[2, :, :, :], min=out[3, :, :, :], max=out[4, :, :, :],
+            argmin=arg[1, :, :, :], argmax=arg[2, :, :, :], members=members, filled=filled[])
 end
 
 """
