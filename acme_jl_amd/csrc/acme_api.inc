@@ -200,6 +200,12 @@ struct acme_batch {
         int *d_ens_member = nullptr;             // the plan (meas_ensemble_plan): instances sorted by (group, instance)
         long long *d_ens_off = nullptr;          // [G + 1]
         double *d_ens_acc = nullptr;             // [6][G nrows][E]: S, Q, min, max, then imin, imax as long long
+        // histogram (acme_batch_set_measurement_histogram): the amplitude distribution of every (instance, row) pair
+        bool hist = false;
+        int hist_B = 0, hist_mode = 0;
+        std::vector<double> hist_range;          // [N][3]: lo_i, hi_i, s_i on the host (the getter's range)
+        long long *d_hist_cnt = nullptr;         // [N nrows][B + 3]: UNDER, BIN[0 ... B - 1], OVER, NAN, from 0
+        double *d_hist_range = nullptr;          // [N][3]
         // weighting (acme_batch_set_measurement_weighting): a biquad cascade ahead of every form; wS = 0: none
         int wS = 0;
         double wsos[MEAS_MAX_WEIGHT_SECTIONS][5] = {};          // b0 b1 b2 a1 a2
@@ -823,6 +829,7 @@ static void meas_release(acme_batch::Measurement &M) {
     (void)be::dfree(M.d_tgt); (void)be::dfree(M.d_tgt_which); (void)be::dfree(M.d_tgt_wuni); (void)be::dfree(M.d_tgt_lag); (void)be::dfree(M.d_tgt_acc);
     (void)be::dfree(M.d_wstate); (void)be::dfree(M.d_yw);
     (void)be::dfree(M.d_ens_member); (void)be::dfree(M.d_ens_off); (void)be::dfree(M.d_ens_acc);
+    (void)be::dfree(M.d_hist_cnt); (void)be::dfree(M.d_hist_range);
     M = acme_batch::Measurement{};
 }
 
@@ -1538,6 +1545,11 @@ static int meas_step(acme_batch *b, const double *y, long long n, long long pitc
             memcpy(G.row, row, sizeof(G.row));
             HIPCHK(meas_ensemble_launch(G, st));
         }
+        if (M.hist) {   // ... and every sample of the chunk into one counter of its pair
+            MeasHistArgs G{y, M.d_hist_cnt, M.d_hist_range, b->N, len, pitch, s - M.pos, M.hist_B, M.hist_mode, A.ny, M.nrows, {}};
+            memcpy(G.row, row, sizeof(G.row));
+            HIPCHK(meas_hist_launch(G, st));
+        }
     }
     M.pos += n;
     return ACME_OK;
@@ -2242,6 +2254,10 @@ static int meas_zero(acme_batch *b) {
         HIPCHK(meas_ensemble_start(M.d_ens_acc, (long long *)(M.d_ens_acc + 4 * plane), plane));
         HIPCHK(be::device_sync());
     }
+    if (M.hist) {       // the counters (bins, mode and the ranges stay)
+        HIPCHK(meas_hist_zero(M.d_hist_cnt, P * (size_t)(M.hist_B + 3)));
+        HIPCHK(be::device_sync());
+    }
     if (M.wS) {         // the sections' states (the coefficients stay)
         HIPCHK(meas_weight_zero(M.d_wstate, P * 2 * (size_t)M.wS));
         HIPCHK(be::device_sync());
@@ -2420,6 +2436,7 @@ int acme_batch_set_measurement_series(acme_batch *b, long long win, long long ho
     if (M.cross) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a cross-spectrum (a cross-spectrum per window is not supported)");
     if (M.target) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a target (a target per window is not supported)");
     if (M.ens) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has an ensemble (an ensemble per window is not supported)");
+    if (M.hist) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a histogram (a histogram per window is not supported)");
     if (M.length != 0) return fail(ACME_ERR_INVALID, "measurement series: the armed measurement's length must be 0 (the series sets the windows)");
     if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement series: samples have been fed since arming (arm or reset the measurement first)");
     if (win < 1) return fail(ACME_ERR_INVALID, "measurement series: win must be >= 1");
@@ -2898,6 +2915,71 @@ int acme_batch_get_measurement_ensemble(acme_batch *b, double *out, long long *a
         for (size_t q = 0; q < plane; ++q)
             for (int k = 0; k < 2; ++k) arg[q * 2 + k] = a[(size_t)k * plane + q];
     }
+    return ACME_OK;
+}
+
+int acme_batch_set_measurement_histogram(acme_batch *b, int bins, int mode, double lo, double hi, const double *lo_i, const double *hi_i) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    acme_batch::Measurement &M = b->meas;
+    if (!M.on) return fail(ACME_ERR_INVALID, "measurement histogram: no measurement is armed");
+    if (M.W) return fail(ACME_ERR_UNSUPPORTED, "measurement histogram: the measurement has a series of windows (a histogram per window is not supported)");
+    if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement histogram: samples have been fed since arming (arm or reset the measurement first)");
+    if (bins < 1 || bins > MEAS_MAX_HIST_BINS)
+        return fail(ACME_ERR_INVALID, "measurement histogram: bins is outside 1 ... " + std::to_string(MEAS_MAX_HIST_BINS));
+    if (mode != MEAS_HIST_SIGNED && mode != MEAS_HIST_ABS)
+        return fail(ACME_ERR_INVALID, "measurement histogram: mode must be ACME_HIST_SIGNED (0) or ACME_HIST_ABS (1)");
+    if ((lo_i == nullptr) != (hi_i == nullptr))
+        return fail(ACME_ERR_INVALID, std::string("measurement histogram: ") + (lo_i ? "hi_i" : "lo_i") + " is NULL beside the other array (both or neither)");
+    const long long PR = b->N * (long long)M.nrows;
+    if (PR > 0 && (long long)(bins + 3) > MEAS_MAX_HISTOGRAM / PR)
+        return fail(ACME_ERR_INVALID, "measurement histogram: N nrows (B + 3) exceeds " + std::to_string(MEAS_MAX_HISTOGRAM));
+    std::vector<double> range((size_t)b->N * 3);
+    for (long long i = 0; i < b->N; ++i) {      // the scale, formed once: two roundings
+        const double l = lo_i ? lo_i[i] : lo, h = hi_i ? hi_i[i] : hi;
+        const std::string at = lo_i ? " of instance " + std::to_string(i) : std::string();
+        const char *ln = lo_i ? "lo_i" : "lo", *hn = lo_i ? "hi_i" : "hi";
+        if (!std::isfinite(l)) return fail(ACME_ERR_INVALID, std::string("measurement histogram: ") + ln + at + " is not finite");
+        if (!std::isfinite(h)) return fail(ACME_ERR_INVALID, std::string("measurement histogram: ") + hn + at + " is not finite");
+        if (l >= h) return fail(ACME_ERR_INVALID, std::string("measurement histogram: ") + ln + " >= " + hn + at);
+        double d, s;
+        meas_hist_scale(l, h, bins, &d, &s);
+        if (!std::isfinite(d)) return fail(ACME_ERR_INVALID, std::string("measurement histogram: ") + hn + " - " + ln + at + " overflows");
+        if (!std::isfinite(s)) return fail(ACME_ERR_INVALID, std::string("measurement histogram: bins / (") + hn + " - " + ln + ")" + at + " overflows");
+        range[(size_t)i * 3] = l; range[(size_t)i * 3 + 1] = h; range[(size_t)i * 3 + 2] = s;
+    }
+    const size_t count = (size_t)PR * (size_t)(bins + 3);
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    (void)be::dfree(M.d_hist_cnt); (void)be::dfree(M.d_hist_range);     // (a histogram set again replaces the earlier one)
+    M.d_hist_cnt = nullptr;
+    M.d_hist_range = nullptr;
+    M.hist = false;
+    HIPCHK(be::dmalloc((void **)&M.d_hist_cnt, sizeof(long long) * std::max<size_t>(count, 1)));
+    HIPCHK(be::dmalloc((void **)&M.d_hist_range, sizeof(double) * std::max<size_t>(range.size(), 1)));
+    if (!range.empty()) HIPCHK(be::copy_h2d(M.d_hist_range, range.data(), sizeof(double) * range.size()));
+    HIPCHK(meas_hist_zero(M.d_hist_cnt, count));
+    HIPCHK(be::device_sync());
+    M.hist_range = std::move(range);
+    M.hist_B = bins;
+    M.hist_mode = mode;
+    M.hist = true;
+    return ACME_OK;
+}
+
+int acme_batch_get_measurement_histogram(acme_batch *b, long long *counts, double *range, long long *count) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const acme_batch::Measurement &M = b->meas;
+    if (!M.on || !M.hist) return fail(ACME_ERR_INVALID, "no measurement histogram is set");
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    const long long end = M.length ? M.start + M.length : LLONG_MAX;
+    const long long cnt = (M.pos < end ? M.pos : end) - M.start;
+    if (count) *count = cnt > 0 ? cnt : 0;
+    if (range && !M.hist_range.empty()) memcpy(range, M.hist_range.data(), sizeof(double) * M.hist_range.size());
+    const size_t n = (size_t)b->N * M.nrows * (size_t)(M.hist_B + 3);
+    if (counts && n) HIPCHK(be::copy_d2h(counts, M.d_hist_cnt, sizeof(long long) * n));     // (the counters' layout is the result's)
     return ACME_OK;
 }
 

@@ -108,6 +108,14 @@
 // waves than the device has SIMDs, ONE tile with the four chains (S | Q | min | max) split over the waves; the emulator walks
 // meas_ensemble_chain.
 //
+// HISTOGRAM (acme_batch_set_measurement_histogram): the amplitude distribution of every pair -- the one accumulator whose
+// ADDRESS depends on the data.  Per sample exactly one of B + 3 integer counters of the pair goes up (meas_hist_bin: NAN,
+// UNDER, OVER or bin k = trunc((x - lo_i) s_i) clamped to B - 1, the difference and the product rounded on their own, the
+// scale s_i = B / (hi_i - lo_i) formed once on the host).  Counters are [n nrows][B + 3] long long in the result's order, the
+// ranges [n][3].  One more kernel per chunk (acme_meas_hist_kernel<AGG>): one wave per pair, LDS atomic adds into the wave's
+// own 32-bit counters, runs of equal counters among neighbouring lanes aggregated first, then a plain add of the non-zero
+// ones into global memory; the pairs of a block follow from B (meas_hist_waves); the emulator walks meas_hist_chain.
+//
 // The per-element functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with g++).
 #pragma once
@@ -464,6 +472,58 @@ inline void meas_ensemble_plan(const int *group, long long n, int G, VI *member,
     for (long long i = 0; i < n; ++i) {     // (ascending i: every group's members in ascending instance order)
         const int g = group ? group[i] : 0;
         if (g >= 0) (*member)[(size_t)at[(size_t)g]++] = (int)i;
+    }
+}
+
+// histogram: every sample of the chunk raises ONE of the B + 3 counters of its (instance, row) pair; cnt is
+// [n * nrows][B + 3] in the result's order (UNDER, BIN[0 ... B - 1], OVER, NAN), range [n][3] = lo_i, hi_i, s_i
+constexpr int MEAS_HIST_SIGNED = 0, MEAS_HIST_ABS = 1;
+constexpr int MEAS_MAX_HIST_BINS = 4096;
+constexpr long long MEAS_MAX_HISTOGRAM = 1ll << 28;     // N nrows (B + 3) counters at most (2 GiB of them)
+constexpr int MEAS_HIST_WAVES = 4;          // pairs (one wave each) per block at most ...
+constexpr int MEAS_HIST_LDS = 32768;        // ... and as many as keep a block's counters within these bytes of LDS
+constexpr int MEAS_HIST_AHEAD = 8;          // loads a lane has in flight
+
+struct MeasHistArgs {
+    const double *y;            // instance i, sample t, row r at y[(i * pitch + t0 + t) * ny + r]
+    long long *cnt;             // [n * nrows][B + 3]
+    const double *range;        // [n][3]: lo, hi, s
+    long long n, len, pitch, t0;
+    int B, mode, ny, nrows;
+    unsigned char row[64];      // the measured rows, ascending
+};
+
+// the scale, formed once at arming with two roundings: d = hi - lo; s = B / d
+ACME_HD ACME_NO_CONTRACT_FN inline void meas_hist_scale(double lo, double hi, int B, double *d, double *s) {
+    ACME_NO_CONTRACT
+    *d = hi - lo;
+    *s = (double)B / *d;
+}
+
+// the counter 0 ... B + 2 of one sample (x = v, or |v| in the ABS mode): the contract of include/acme_hip.h, the difference
+// and the product rounded on their own
+ACME_HD ACME_NO_CONTRACT_FN inline int meas_hist_bin(double x, double lo, double hi, double s, int B) {
+    ACME_NO_CONTRACT
+    if (x != x) return B + 2;
+    if (x < lo) return 0;
+    if (x >= hi) return B + 1;
+    const double t = x - lo;
+    const double q = t * s;
+    long long k = (long long)q;         // truncation; q >= 0 here (-0.0 at lo = 0 included)
+    if (k > B - 1) k = B - 1;           // q can round up to B just below hi
+    return (int)k + 1;
+}
+
+// one pair over the chunk, sample after sample (the plain loop of the non-HIP backend; counters are integers, any order
+// gives the same result)
+ACME_HD inline void meas_hist_chain(const MeasHistArgs &A, long long p) {
+    const long long i = p / A.nrows;
+    const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    const double lo = A.range[3 * i], hi = A.range[3 * i + 1], s = A.range[3 * i + 2];
+    long long *c = A.cnt + p * (A.B + 3);
+    for (long long t = 0; t < A.len; ++t) {
+        const double v = yp[t * A.ny];
+        c[meas_hist_bin(A.mode == MEAS_HIST_ABS ? fabs(v) : v, lo, hi, s, A.B)] += 1;
     }
 }
 
@@ -1514,7 +1574,85 @@ __global__ __launch_bounds__(256) void acme_meas_ens_start_kernel(double *acc, l
     const long long at = (long long)blockIdx.x * 256 + threadIdx.x;
     if (at < plane) acme::meas_ens_start(acc, arg, plane, at);
 }
+
+// histogram: ONE WAVE PER PAIR (the range, the scale and the pair's addresses are wave-uniform), `waves` pairs a block.  The
+// wave's lanes stride over the chunk's samples, MEAS_HIST_AHEAD loads each in flight; a sample's counter (meas_hist_bin) goes
+// up by LDS integer atomic add in the wave's own B + 3 counters of 32 bits (a chunk is at most MEAS_CHUNK samples); the lanes
+// then add the non-zero ones into the pair's 64-bit counters in global memory with plain load / add / store -- nobody else
+// owns the pair.  AGG: neighbouring lanes hold neighbouring samples, so on a constant or slowly moving signal they hit ONE
+// counter and the atomics serialise; the first lane of each run of equal counters among neighbouring lanes (one DPP shift, one
+// ballot) adds the run's length instead.  Counts are integers: both shapes give the same result.
+__device__ inline void acme_meas_hist_add_runs(unsigned int *h, int k, int lane) {
+    const int prev = __builtin_amdgcn_update_dpp(k, k, 0x138, 0xf, 0xf, false);     // wave_shr:1 (lane 0 keeps its own)
+    const bool head = lane == 0 || prev != k;
+    const unsigned long long heads = __ballot(head);
+    const unsigned long long above = lane == 63 ? 0ull : heads >> (lane + 1);       // the heads above this lane
+    const int run = above ? __builtin_ctzll(above) + 1 : 64 - lane;
+    if (head && k >= 0) atomicAdd(&h[k], (unsigned int)run);
+}
+template <bool AGG>
+__global__ __launch_bounds__(64 * acme::MEAS_HIST_WAVES) void acme_meas_hist_kernel(acme::MeasHistArgs A, int waves) {
+    using namespace acme;
+    extern __shared__ unsigned int acme_meas_hist_lds[];
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), C = A.B + 3;
+    const long long p = (long long)blockIdx.x * waves + wave;
+    const bool live = p < A.n * A.nrows;                // (wave-uniform; every wave of the block reaches both barriers)
+    unsigned int *h = acme_meas_hist_lds + wave * C;
+    for (int c = lane; c < C; c += 64) h[c] = 0u;
+    __syncthreads();
+    if (live) {
+        const long long i = p / A.nrows;
+        const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+        const double lo = A.range[3 * i], hi = A.range[3 * i + 1], s = A.range[3 * i + 2];
+        const bool rect = A.mode == MEAS_HIST_ABS;
+        for (long long tb = 0; tb < A.len; tb += 64 * MEAS_HIST_AHEAD) {
+            double v[MEAS_HIST_AHEAD];
+            bool on[MEAS_HIST_AHEAD];
+#pragma unroll
+            for (int u = 0; u < MEAS_HIST_AHEAD; ++u) {     // the loads are in flight together
+                const long long t = tb + 64 * u + lane;
+                on[u] = t < A.len;
+                v[u] = on[u] ? yp[t * A.ny] : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < MEAS_HIST_AHEAD; ++u) {
+                const int k = on[u] ? meas_hist_bin(rect ? fabs(v[u]) : v[u], lo, hi, s, A.B) : -1;
+                if (AGG) acme_meas_hist_add_runs(h, k, lane);
+                else if (k >= 0) atomicAdd(&h[k], 1u);
+            }
+        }
+    }
+    __syncthreads();
+    if (live) {
+        long long *g = A.cnt + p * C;
+        for (int c = lane; c < C; c += 64) {
+            const unsigned int n = h[c];
+            if (n) g[c] += (long long)n;
+        }
+    }
+}
 namespace acme {
+// the pairs of a block: as many waves as keep the block's counters within MEAS_HIST_LDS bytes, MEAS_HIST_WAVES at most
+inline int meas_hist_waves(int B) {
+    const int w = MEAS_HIST_LDS / ((B + 3) * (int)sizeof(unsigned int));
+    return w < 1 ? 1 : w > MEAS_HIST_WAVES ? MEAS_HIST_WAVES : w;
+}
+// the runs of equal counters aggregated before the atomic unless ACME_HIST_AGG=0 in the environment (A/B measurements, tests)
+inline bool meas_hist_agg() {
+    const char *e = getenv("ACME_HIST_AGG");
+    return !(e && e[0] == '0');
+}
+inline int meas_hist_launch(const MeasHistArgs &A, hipStream_t st) {
+    const long long pairs = A.n * A.nrows;
+    if (pairs <= 0 || A.len <= 0) return 0;
+    const int w = meas_hist_waves(A.B);
+    const unsigned blocks = (unsigned)((pairs + w - 1) / w);
+    const size_t lds = sizeof(unsigned int) * (size_t)w * (size_t)(A.B + 3);
+    if (meas_hist_agg()) hipLaunchKernelGGL(acme_meas_hist_kernel<true>, dim3(blocks), dim3(64 * w), lds, st, A, w);
+    else hipLaunchKernelGGL(acme_meas_hist_kernel<false>, dim3(blocks), dim3(64 * w), lds, st, A, w);
+    return (int)hipGetLastError();
+}
+inline int meas_hist_zero(long long *cnt, size_t count) { return count ? (int)hipMemset(cnt, 0, sizeof(long long) * count) : 0; }
 // SPLIT where the unsplit launch would leave SIMDs without a wave; ACME_ENS_SPLIT=0 / 1 in the environment forces one (A/B
 // measurements, tests)
 inline bool meas_ens_split(long long pairs, long long nrec) {
@@ -1791,6 +1929,14 @@ inline int meas_ensemble_launch(const MeasEnsArgs &A, void *) {
 }
 inline int meas_ensemble_start(double *acc, long long *arg, size_t plane) {
     for (size_t at = 0; at < plane; ++at) meas_ens_start(acc, arg, (long long)plane, (long long)at);
+    return 0;
+}
+inline int meas_hist_launch(const MeasHistArgs &A, void *) {
+    for (long long p = 0; p < A.n * A.nrows; ++p) meas_hist_chain(A, p);
+    return 0;
+}
+inline int meas_hist_zero(long long *cnt, size_t count) {
+    std::fill(cnt, cnt + count, 0ll);
     return 0;
 }
 inline int meas_fold_launch(const MeasFoldArgs &A, void *) {

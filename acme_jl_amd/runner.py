@@ -74,6 +74,7 @@ ABI_SYMBOLS = [
     "acme_batch_set_measurement_target", "acme_batch_get_measurement_target",
     "acme_batch_set_measurement_weighting", "acme_batch_get_measurement_weighting",
     "acme_batch_set_measurement_ensemble", "acme_batch_get_measurement_ensemble",
+    "acme_batch_set_measurement_histogram", "acme_batch_get_measurement_histogram",
 ]
 
 SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE, SOURCE_NOISE = 1, 2, 3, 4, 5
@@ -83,6 +84,9 @@ MAX_FOLD_PERIOD = 65536
 MAX_TARGETS = 64
 MAX_WEIGHTING_SECTIONS = 8
 MAX_ENSEMBLE = 16777216
+HIST_SIGNED, HIST_ABS = 0, 1
+MAX_HIST_BINS = 4096
+MAX_HISTOGRAM = 268435456
 _SOURCE_KINDS = {"const": SOURCE_CONST, "sine": SOURCE_SINE, "table": SOURCE_TABLE, "multisine": SOURCE_MULTISINE, "noise": SOURCE_NOISE,
                  SOURCE_CONST: SOURCE_CONST, SOURCE_SINE: SOURCE_SINE, SOURCE_TABLE: SOURCE_TABLE, SOURCE_MULTISINE: SOURCE_MULTISINE,
                  SOURCE_NOISE: SOURCE_NOISE}
@@ -219,6 +223,8 @@ class Library:
         L.acme_batch_get_measurement_target.argtypes = [vp, dp, lp]
         L.acme_batch_set_measurement_ensemble.argtypes = [vp, ip, C.c_int, C.c_longlong]
         L.acme_batch_get_measurement_ensemble.argtypes = [vp, dp, lp, lp, lp]
+        L.acme_batch_set_measurement_histogram.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, dp, dp]
+        L.acme_batch_get_measurement_histogram.argtypes = [vp, lp, dp, lp]
         L.acme_batch_set_measurement_weighting.argtypes = [vp, dp, C.c_int]
         L.acme_batch_get_measurement_weighting.argtypes = [vp, dp, C.POINTER(C.c_int)]
 
@@ -633,6 +639,100 @@ class MeasurementEnsemble:
         return cls(*out, members, a.filled, a.stride, a.rows)
 
 
+class MeasurementHistogram:
+    """What ``ModelRunner.measurement_histogram()`` returns: the amplitude distribution of every (instance, measured row).
+    ``counts`` (N, nrows, B) int64: bin k of instance i holds the samples with ``x`` in ``[edges(i)[k], edges(i)[k + 1])``
+    (``x`` the measured value, its magnitude in the ``"abs"`` mode); ``under``, ``over``, ``nan`` (N, nrows): the samples below
+    ``lo``, at or above ``hi`` and not a number; ``count``: the samples measured -- ``counts.sum(-1) + under + over + nan ==
+    count`` for every pair; ``lo``, ``hi``, ``scale`` (N,): the instances' ranges and ``B / (hi - lo)`` as the library stored
+    them; ``mode`` ``"signed"`` or ``"abs"``; ``rows`` the measured output rows.
+
+    The helpers work on the samples that have a value, ``count - nan`` of them (a pair with none reads NaN), and know nothing
+    finer than a bin: at a bin edge they are exact, inside a bin they take the bin's samples as spread evenly over it."""
+
+    def __init__(self, counts, under, over, nan, count, lo, hi, scale, mode, rows):
+        self.counts, self.under, self.over, self.nan = counts, under, over, nan
+        self.count, self.mode, self.rows = int(count), mode, tuple(rows)
+        self.lo, self.hi, self.scale = (np.asarray(a, dtype=np.float64) for a in (lo, hi, scale))
+
+    @property
+    def bins(self):
+        return self.counts.shape[-1]
+
+    def edges(self, i):
+        """the B + 1 nominal bin edges of instance ``i``: ``lo + k / scale``, the last one ``hi`` itself (at an edge the
+        library's two roundings decide the side a sample falls on)"""
+        e = self.lo[i] + np.arange(self.bins + 1) / self.scale[i]
+        e[-1] = self.hi[i]
+        return e
+
+    def _valued(self):
+        n = (self.count - self.nan).astype(np.float64)
+        return np.where(n > 0, n, np.nan)
+
+    def _cumulative(self):
+        """(N, nrows, B + 1): the samples below edge k"""
+        return np.concatenate([self.under[..., None], self.under[..., None] + np.cumsum(self.counts, axis=-1)], axis=-1)
+
+    def pdf(self):
+        """the density per unit of ``x`` (N, nrows, B): ``counts scale / (count - nan)``; its integral over the range is the
+        share of the samples inside it"""
+        return self.counts * self.scale[:, None, None] / self._valued()[..., None]
+
+    def cdf(self):
+        """the share of the samples below each edge (N, nrows, B + 1): ``cdf()[..., 0]`` the share in ``under``,
+        ``1 - cdf()[..., -1]`` the share in ``over``; exact"""
+        return self._cumulative() / self._valued()[..., None]
+
+    def percentile(self, q):
+        """the level below which ``q`` percent of the samples lie (N, nrows), or (len(q), N, nrows) for a sequence: linear
+        inside the bin that holds the rank, NaN where the answer lies in ``under`` or ``over`` (outside the range)"""
+        if np.ndim(q) > 0:
+            return np.stack([self.percentile(v) for v in q])
+        B, cum, n = self.bins, self._cumulative().astype(np.float64), self._valued()
+        target = float(q) / 100.0 * n
+        with np.errstate(invalid="ignore", divide="ignore"):
+            k = (cum <= target[..., None]).sum(axis=-1) - 1         # the last edge with no more than the rank below it
+            inside = (k >= 0) & (k < B)
+            kk = np.clip(k, 0, B - 1)
+            below = np.take_along_axis(cum, kk[..., None], axis=-1)[..., 0]
+            inbin = np.take_along_axis(self.counts, kk[..., None], axis=-1)[..., 0]
+            x = self.lo[:, None] + (kk + (target - below) / inbin) / self.scale[:, None]
+            top = (k == B) & (target == cum[..., B])                # the rank sits exactly on the last edge
+            return np.where(inside, x, np.where(top, self.hi[:, None], np.nan))
+
+    def fraction_below(self, x):
+        """the share of the samples with a value below ``x`` (a scalar or N values, one per instance), (N, nrows): exact where
+        ``x`` is a bin edge, interpolated linearly inside a bin; for an ``x`` outside ``[lo, hi]`` 0.0 / 1.0 where ``under`` /
+        ``over`` hold nothing, NaN where they hold samples (the range did not resolve them)"""
+        B, cum = self.bins, self._cumulative().astype(np.float64)
+        xv = np.broadcast_to(np.asarray(x, dtype=np.float64), self.lo.shape)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            pos = np.where(xv == self.hi, float(B), (xv - self.lo) * self.scale)     # in bins from lo
+            ok = (xv >= self.lo) & (xv <= self.hi)
+            k = np.clip(np.floor(np.where(ok, pos, 0.0)), 0, B).astype(np.int64)
+            frac = np.where(ok, pos, 0.0) - k
+            at = np.take_along_axis(cum, np.broadcast_to(k[:, None, None], cum.shape[:2] + (1,)), axis=-1)[..., 0]
+            nxt = np.take_along_axis(cum, np.broadcast_to(np.minimum(k + 1, B)[:, None, None], cum.shape[:2] + (1,)), axis=-1)[..., 0]
+            inside = (at + frac[:, None] * (nxt - at)) / self._valued()
+            low = np.where(self.under == 0, 0.0 * self._valued(), np.nan)           # (NaN too for a pair without a valued sample)
+            high = np.where(self.over == 0, 1.0 + 0.0 * self._valued(), np.nan)
+            return np.where(ok[:, None], inside, np.where((xv < self.lo)[:, None], low, np.where((xv > self.hi)[:, None], high, np.nan)))
+
+    def fraction_above(self, x):
+        """the share of the samples with a value at or above ``x``: ``1 - fraction_below(x)``"""
+        return 1.0 - self.fraction_below(x)
+
+    @classmethod
+    def concatenate(cls, parts):
+        """several batches' results (the shards of ``MultiDeviceRunner``) as one, along the instances"""
+        a = parts[0]
+        if any((p.count, p.mode, p.rows, p.bins) != (a.count, a.mode, a.rows, a.bins) for p in parts):
+            raise ValueError("the shards' histograms differ in their sample counts, modes, bins or measured rows")
+        cat = lambda k: np.concatenate([getattr(p, k) for p in parts])
+        return cls(cat("counts"), cat("under"), cat("over"), cat("nan"), a.count, cat("lo"), cat("hi"), cat("scale"), a.mode, a.rows)
+
+
 class MeasurementWeighting:
     """What ``ModelRunner.measurement_weighting()`` returns, and what ``set_measurement_weighting`` accepts: a cascade of
     second-order sections, ``sos`` (S, 5) with the rows ``b0 b1 b2 a1 a2`` of
@@ -878,6 +978,7 @@ class ModelRunner:
         self._target = False            # a target is set on the armed measurement
         self._weighting = False         # a weighting is set on the armed measurement
         self._ensemble = None           # (G, stride, E) of the ensemble set on the armed measurement
+        self._histogram = None          # (B, mode) of the histogram set on the armed measurement
         self._length = 0                # the armed measurement's window length (0: unbounded)
         self._sources = {}              # input row -> kind, while the row has a source
         self._sine = {}                 # input row -> (f_den, f_num as armed) of its sine source
@@ -976,6 +1077,7 @@ class ModelRunner:
         self._target = False
         self._weighting = False
         self._ensemble = None
+        self._histogram = None
         return self
 
     def set_measurement_bins(self, coef, start=0, length=0, rows=None, f_den=None, f_num=None, tones_from_source=None):
@@ -1017,6 +1119,7 @@ class ModelRunner:
         self._target = False
         self._weighting = False
         self._ensemble = None
+        self._histogram = None
         return self
 
     def measurement_plan(self):
@@ -1043,6 +1146,7 @@ class ModelRunner:
         self._target = False
         self._weighting = False
         self._ensemble = None
+        self._histogram = None
         return self
 
     def set_measurement_series(self, win, hop=None, windows=1):
@@ -1301,6 +1405,41 @@ class ModelRunner:
                                                                       members.ctypes.data_as(lp), C.byref(filled)))
         return MeasurementEnsemble(*(out[..., k].copy() for k in range(4)), arg[..., 0].copy(), arg[..., 1].copy(), members,
                                    filled.value, stride, rows)
+
+    def set_measurement_histogram(self, bins, lo, hi, mode="signed"):
+        """Count how the amplitude of every measured row is distributed (``acme_batch_set_measurement_histogram``): ``bins``
+        equal bins over ``[lo, hi)`` per instance plus the samples below, at or above the range and not a number -- levels
+        exceeded, percentiles and the density with no y stored.  ``lo``, ``hi``: scalars, or N values each (a scalar beside
+        an array is repeated); ``mode``: ``"signed"`` or ``"abs"`` (the magnitude is binned).  Needs an armed measurement
+        that has not been fed yet; not together with a series; ``measurement_histogram`` reads it."""
+        if self._meas is None:
+            raise AcmeError("no measurement is armed")
+        modes = {"signed": HIST_SIGNED, "abs": HIST_ABS, HIST_SIGNED: HIST_SIGNED, HIST_ABS: HIST_ABS}
+        if mode not in modes:
+            raise ValueError(f"mode must be 'signed' or 'abs', not {mode!r}")
+        if np.ndim(lo) == 0 and np.ndim(hi) == 0:
+            self.lib.check(self.lib.L.acme_batch_set_measurement_histogram(self.h, int(bins), modes[mode], float(lo), float(hi), None, None))
+        else:
+            for name, a in (("lo", lo), ("hi", hi)):
+                if np.ndim(a) != 0 and np.shape(a) != (self.n,):
+                    raise DimensionMismatch(f"{name} needs {self.n} values (or a scalar)")
+            la = np.ascontiguousarray(np.broadcast_to(np.asarray(lo, dtype=np.float64), (self.n,)))
+            ha = np.ascontiguousarray(np.broadcast_to(np.asarray(hi, dtype=np.float64), (self.n,)))
+            self.lib.check(self.lib.L.acme_batch_set_measurement_histogram(self.h, int(bins), modes[mode], 0.0, 0.0, _dp(la), _dp(ha)))
+        self._histogram = (int(bins), "abs" if modes[mode] == HIST_ABS else "signed")
+        return self
+
+    def measurement_histogram(self):
+        """the counters so far (``acme_batch_get_measurement_histogram``): a ``MeasurementHistogram``"""
+        if self._meas is None or self._histogram is None:
+            raise AcmeError("no measurement histogram is set")
+        rows = self._meas[1]
+        B, mode = self._histogram
+        raw, rng, count = np.empty((self.n, len(rows), B + 3), dtype=np.int64), np.empty((self.n, 3)), C.c_longlong(0)
+        self.lib.check(self.lib.L.acme_batch_get_measurement_histogram(self.h, raw.ctypes.data_as(C.POINTER(C.c_longlong)), _dp(rng),
+                                                                       C.byref(count)))
+        return MeasurementHistogram(raw[..., 1:B + 1].copy(), raw[..., 0].copy(), raw[..., B + 1].copy(), raw[..., B + 2].copy(),
+                                    count.value, rng[:, 0].copy(), rng[:, 1].copy(), rng[:, 2].copy(), mode, rows)
 
     def reset_measurement(self):
         """zero the accumulators and restart the window's clock (``acme_batch_reset_measurement``)"""
@@ -2016,6 +2155,22 @@ class MultiDeviceRunner:
         """the shards' ``MeasurementEnsemble`` results joined by group, the indices those of the whole batch"""
         live = [(r, lo) for r, (lo, hi) in zip(self.runners, self.ranges) if r is not None]
         return MeasurementEnsemble.join([r.measurement_ensemble() for r, _ in live], [lo for _, lo in live])
+
+    def set_measurement_histogram(self, bins, lo, hi, mode="signed"):
+        """``ModelRunner.set_measurement_histogram`` on every device's batch, ``lo`` and ``hi`` (scalars or N values) sliced
+        over the devices' instances"""
+        for name, a in (("lo", lo), ("hi", hi)):
+            if np.ndim(a) != 0 and np.shape(a) != (self.n,):
+                raise DimensionMismatch(f"{name} needs {self.n} values (or a scalar)")
+        part = lambda a, lo_, hi_: a if np.ndim(a) == 0 else np.asarray(a)[lo_:hi_]
+        for r, (a, b) in zip(self.runners, self.ranges):
+            if r is not None:
+                r.set_measurement_histogram(bins, part(lo, a, b), part(hi, a, b), mode)
+        return self
+
+    def measurement_histogram(self):
+        """the shards' ``MeasurementHistogram`` results, concatenated along the instances (nothing joins across shards)"""
+        return MeasurementHistogram.concatenate([r.measurement_histogram() for r in self.runners if r is not None])
 
     def set_measurement_weighting(self, sos):
         """``ModelRunner.set_measurement_weighting`` on every device's batch: the same cascade everywhere"""

@@ -585,6 +585,61 @@ int acme_batch_set_measurement_ensemble(acme_batch *b, const int *group /* host 
  * synchronises the device. */
 int acme_batch_get_measurement_ensemble(acme_batch *b, double *out /* [G][nrows][E][4] */, long long *arg /* [G][nrows][E][2] */,
                                         long long *members /* [G] */, long long *filled);
+/* A HISTOGRAM of the window: the armed measurement (any of the three forms, any start / length, bounded or not, no sample fed
+ * since arming or the last reset) also counts HOW THE AMPLITUDE IS DISTRIBUTED, per instance and measured row -- the share of
+ * the window an output spends above a level (time in clipping across a drive sweep, the probability of overload across
+ * Monte-Carlo draws), the median and any percentile (L10 / L50 / L90 of a noise-loaded run, the 99.9 % level as a robust peak),
+ * the density itself (a clipper's pile-up at the rails, a comparator's two modes, asymmetry, dead zones), and the rectified
+ * form of each.  B + 3 integer counters per pair in place of y [N][T][ny].
+ *   bins     B, 1 ... ACME_MAX_HIST_BINS; N nrows (B + 3) <= ACME_MAX_HISTOGRAM
+ *   mode     ACME_HIST_SIGNED: x = v;  ACME_HIST_ABS: x = |v|.  v is the value the other forms see (the weighted row behind a
+ *            weighting, the base-rate row after the decimation of an oversampled batch)
+ *   lo, hi   the range of every instance, finite, lo < hi -- used iff lo_i and hi_i are NULL
+ *   lo_i, hi_i   HOST arrays [N], both or neither: instance i's own range (a drive sweep's range scales with the level);
+ *            copied by the call, lo and hi are then ignored
+ * The scale of instance i is formed ONCE, on the host, with two roundings -- d = hi_i - lo_i;  s_i = (double)B / d -- and
+ * stored; the getter hands it back, so that a replay uses the same bits.  Per sample EXACTLY ONE of the B + 3 counters of its
+ * (instance, row) goes up by one:
+ *   if (x != x)          NAN   += 1
+ *   else if (x < lo_i)   UNDER += 1
+ *   else if (x >= hi_i)  OVER  += 1
+ *   else { t = x - lo_i;  q = t * s_i;       each rounded on its own, NO fused multiply-add
+ *          k = (long long)q;                 truncation; q >= 0 here
+ *          if (k > B - 1) k = B - 1;         q can round up to B just below hi_i
+ *          BIN[k] += 1 }
+ * Bins are half-open: x == lo_i is bin 0, x == hi_i is OVER; -0.0 with lo_i = 0 is bin 0; +inf is OVER and -inf UNDER (in
+ * the ABS mode both are OVER); a NaN -- every sample of an instance from its first_nonfinite sample on -- counts in NAN and
+ * touches no other pair.  Bin k nominally covers [lo_i + k / s_i, lo_i + (k + 1) / s_i); AT an edge the two roundings of t and
+ * q decide on which side a value falls, and the rule above is the definition.  Counters are 64-bit integers, so the result
+ * depends on nothing but the run's samples: chunk, slice and call boundaries, host or device memory, the entry point
+ * (acme_batch_run, _run_const, _run_async, _run_sources), the oversampling factor, a weighting beyond what it feeds as v and
+ * whether y is stored change none of its bits.  The measurement's own accumulators, plan, launches and getter are what they
+ * are without a histogram; it takes one more kernel per chunk of the window and 8 (B + 3) bytes per pair plus 24 bytes per
+ * instance of device memory.  A fold, a spectrum, a cross-spectrum, a target, a weighting, an ensemble and a histogram may
+ * all be set together.
+ * ACME_ERR_INVALID (the message names the argument, and the instance of an entry of lo_i / hi_i): no measurement armed,
+ * samples already fed, bins outside 1 ... ACME_MAX_HIST_BINS, an unknown mode, a non-finite bound, lo_i >= hi_i, hi_i - lo_i
+ * overflowing to infinity (or so small that B / d does), one array without the other, N nrows (B + 3) beyond
+ * ACME_MAX_HISTOGRAM.  ACME_ERR_UNSUPPORTED together with a series, whichever is set first: a histogram per window is not
+ * available.  Setting a histogram again replaces the earlier one.  _reset_measurement zeroes the counters and keeps bins,
+ * mode and the ranges; arming any form or _clear_measurement removes the histogram; acme_batch_set_matrices carries it with
+ * the accumulators; the refusal together with acme_batch_set_isolation is the measurement's own.  A batch without a histogram
+ * launches, allocates and synchronises what it always did.
+ * Out of scope: ranges per ROW (one range per instance serves all its measured rows); logarithmic (dB) bins -- log is not
+ * reproducible bit for bit; automatic ranging -- the recipe is a first run with the plain measurement for min / max, then
+ * _reset_measurement and the histogram. */
+#define ACME_HIST_SIGNED 0
+#define ACME_HIST_ABS    1
+#define ACME_MAX_HIST_BINS 4096
+#define ACME_MAX_HISTOGRAM 268435456        /* N nrows (B + 3) counters at most */
+int acme_batch_set_measurement_histogram(acme_batch *b, int bins, int mode, double lo, double hi,
+                                         const double *lo_i /* host [N] or NULL */, const double *hi_i /* host [N] or NULL */);
+/* the counters so far (each argument may be NULL): counts[N][nrows][B + 3] -- [0] UNDER, [1 ... B] BIN[0 ... B - 1], [B + 1]
+ * OVER, [B + 2] NAN --, range[N][3] = lo_i, hi_i, s_i as stored, *count the samples measured, as acme_batch_get_measurement
+ * counts them: the B + 3 counters of every pair sum to it exactly.  ACME_ERR_INVALID without a histogram.  Joins a pending
+ * acme_batch_run_async and synchronises the device. */
+int acme_batch_get_measurement_histogram(acme_batch *b, long long *counts /* [N][nrows][B + 3] */,
+                                         double *range /* [N][3]: lo_i, hi_i, s_i */, long long *count);
 /* switch the measurement off (y = NULL is refused again) */
 int acme_batch_clear_measurement(acme_batch *b);
 /* zero the accumulators and restart the window's clock (the armed parameters stay) */

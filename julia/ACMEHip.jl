@@ -40,7 +40,8 @@ export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host
        set_source_multisine!, set_source_noise!, set_measurement_bins!, set_measurement_series!, measurement_series,
        set_measurement_fold!, measurement_fold, set_measurement_spectrum!, measurement_spectrum,
        set_measurement_cross!, measurement_cross, set_measurement_target!, measurement_target,
-       set_measurement_weighting!, measurement_weighting, set_measurement_ensemble!, measurement_ensemble
+       set_measurement_weighting!, measurement_weighting, set_measurement_ensemble!, measurement_ensemble,
+       set_measurement_histogram!, measurement_histogram
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
 
@@ -58,6 +59,9 @@ const ACME_MAX_SPECTRUM = 4096
 const ACME_MAX_TARGETS = 64
 const ACME_MAX_WEIGHTING_SECTIONS = 8
 const ACME_MAX_ENSEMBLE = 16777216
+const ACME_HIST_SIGNED, ACME_HIST_ABS = Cint(0), Cint(1)
+const ACME_MAX_HIST_BINS = 4096
+const ACME_MAX_HISTOGRAM = 268435456
 const ACME_SOURCE_CONST, ACME_SOURCE_SINE, ACME_SOURCE_TABLE, ACME_SOURCE_MULTISINE = Cint(1), Cint(2), Cint(3), Cint(4)
 const ACME_SOURCE_NOISE = Cint(5)
 const ACME_NOISE_UNIFORM, ACME_NOISE_GAUSSIAN = Cint(0), Cint(1)
@@ -228,6 +232,7 @@ mutable struct BatchRunner
     spectrum::Int                     # nfft of the spectrum set on the armed measurement (0: none)
     cross::Int                        # nfft of the cross-spectrum set on the armed measurement (0: none)
     ensemble::Tuple{Int,Int}          # (G, stride) of the ensemble set on the armed measurement ((0, 0): none)
+    histogram::Int                    # the bins B of the histogram set on the armed measurement (0: none)
 end
 
 # @showprogress of run!(runner, y, u) (src/ACME.jl:587-604,653): the library reports after every time slice of a
@@ -246,7 +251,7 @@ function BatchRunner(model::DiscreteModel, n::Integer; device::Integer=-1,
     b = Ref{Ptr{Cvoid}}()
     check(ccall((:acme_batch_create, lib), Cint, (Ptr{Cvoid}, Clonglong, Ref{AcmeOptions}, Ref{Ptr{Cvoid}}),
                 mh.h, n, opts, b))
-    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress, nothing, Set{Int}(), 0, 0, (0, 0))
+    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress, nothing, Set{Int}(), 0, 0, (0, 0), 0)
     finalizer(r -> ccall((:acme_batch_destroy, lib), Cvoid, (Ptr{Cvoid},), r.h), r)
     if showprogress
         cb = @cfunction(progress_trampoline, Cvoid, (Ptr{Cvoid}, Clonglong, Clonglong))
@@ -491,6 +496,7 @@ function set_measurement!(r::BatchRunner, spec::MeasureSpec)
     r.spectrum = 0
     r.cross = 0
     r.ensemble = (0, 0)
+    r.histogram = 0
     return r
 end
 function set_measurement!(r::BatchRunner; f_den=nothing, f_num=nothing, kwargs...)
@@ -516,6 +522,7 @@ function set_measurement!(r::BatchRunner, spec::MeasureSpec, f_den::Int64, f_num
     r.spectrum = 0
     r.cross = 0
     r.ensemble = (0, 0)
+    r.histogram = 0
     return r
 end
 
@@ -542,6 +549,7 @@ function set_measurement_bins!(r::BatchRunner, coef::Matrix{<:Integer}, f_den::I
     r.spectrum = 0
     r.cross = 0
     r.ensemble = (0, 0)
+    r.histogram = 0
     return r
 end
 
@@ -570,6 +578,7 @@ function clear_measurement!(r::BatchRunner)
     r.spectrum = 0
     r.cross = 0
     r.ensemble = (0, 0)
+    r.histogram = 0
     return r
 end
 
@@ -887,6 +896,53 @@ function measurement_ensemble(r::BatchRunner)
                 (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Clonglong}, Ptr{Clonglong}, Ref{Clonglong}), r.h, out, arg, members, filled))
     return (sum=out[1, :, :, :], sumsq=out[2, :, :, :], min=out[3, :, :, :], max=out[4, :, :, :],
             argmin=arg[1, :, :, :], argmax=arg[2, :, :, :], members=members, filled=filled[])
+end
+
+"""
+    set_measurement_histogram!(runner, bins, lo, hi; mode=:signed)
+
+Count how the amplitude of every measured row is distributed (`acme_batch_set_measurement_histogram`): `bins` equal bins over
+`[lo, hi)` per instance plus the samples below, at or above the range and not a number.  `lo`, `hi`: two numbers, or two
+vectors with one entry per instance; `mode` `:signed` or `:abs` (the magnitude is binned).  Needs an armed measurement that has
+not been fed yet; not together with a series.
+"""
+function set_measurement_histogram!(r::BatchRunner, bins::Integer, lo, hi; mode::Symbol=:signed)
+    r.meas === nothing && error("no measurement is armed")
+    mode in (:signed, :abs) || throw(ArgumentError("mode must be :signed or :abs"))
+    (lo isa Number) == (hi isa Number) || throw(ArgumentError("lo and hi are both numbers or both vectors"))
+    m = mode === :abs ? ACME_HIST_ABS : ACME_HIST_SIGNED
+    if lo isa Number
+        check(ccall((:acme_batch_set_measurement_histogram, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Cint, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}), r.h, bins, m, lo, hi, C_NULL, C_NULL))
+    else
+        l, h = perinstance(Float64, lo, r.n), perinstance(Float64, hi, r.n)
+        GC.@preserve l h check(ccall((:acme_batch_set_measurement_histogram, lib), Cint,
+                    (Ptr{Cvoid}, Cint, Cint, Cdouble, Cdouble, Ptr{Cdouble}, Ptr{Cdouble}), r.h, bins, m, 0.0, 0.0, pointer(l), pointer(h)))
+    end
+    r.histogram = Int(bins)
+    return r
+end
+
+"""
+    measurement_histogram(runner) -> (counts, under, over, nan, lo, hi, scale, count)
+
+The counters so far (`acme_batch_get_measurement_histogram`), for the bins that `set_measurement_histogram!` set (the runner
+keeps them and sizes the arrays): `counts` `B x nrows x N`, `under`, `over`, `nan` `nrows x N`, the instances' ranges and
+scales `B / (hi - lo)` as stored, and `count`, the samples measured -- every pair's counters sum to it.
+"""
+function measurement_histogram(r::BatchRunner)
+    spec = r.meas
+    B = r.histogram
+    (spec === nothing || B == 0) && error("no measurement histogram is set")
+    ny = ACME.ny(r.model)
+    nrows = spec.rows == 0 ? min(ny, 64) : count_ones(spec.rows)
+    raw = Array{Int64,3}(undef, B + 3, nrows, r.n)                   # the ABI's [N][nrows][B + 3]
+    range = Matrix{Float64}(undef, 3, r.n)                           # ... and [N][3]
+    count = Ref{Clonglong}(0)
+    check(ccall((:acme_batch_get_measurement_histogram, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Clonglong}, Ptr{Cdouble}, Ref{Clonglong}), r.h, raw, range, count))
+    return (counts=raw[2:B + 1, :, :], under=raw[1, :, :], over=raw[B + 2, :, :], nan=raw[B + 3, :, :],
+            lo=range[1, :], hi=range[2, :], scale=range[3, :], count=count[])
 end
 
 """
