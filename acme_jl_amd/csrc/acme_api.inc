@@ -206,6 +206,16 @@ struct acme_batch {
         std::vector<double> hist_range;          // [N][3]: lo_i, hi_i, s_i on the host (the getter's range)
         long long *d_hist_cnt = nullptr;         // [N nrows][B + 3]: UNDER, BIN[0 ... B - 1], OVER, NAN, from 0
         double *d_hist_range = nullptr;          // [N][3]
+        // events (acme_batch_set_measurement_events): level crossings of every (instance, row, level) triple
+        bool events = false;
+        int ev_C = 0, ev_E = 0;
+        std::vector<double> ev_lev;              // [2][C][N]: lo, then hi, on the host
+        double *d_ev_lev = nullptr;              // [2][C][N]
+        long long *d_ev_cnt = nullptr;           // [N nrows C][5]: RISE, FALL, HIGH, LOW, UNKNOWN
+        long long *d_ev_idx = nullptr;           // [N nrows C][2][E + 1]: the events' window samples, -1: empty
+        double *d_ev_ab = nullptr;               // [N nrows C][2][E + 1][2]: v[m - 1], v[m]
+        int *d_ev_state = nullptr;               // the carry: [N nrows C] states ...
+        double *d_ev_prev = nullptr;             // ... and [N nrows] last window samples
         // weighting (acme_batch_set_measurement_weighting): a biquad cascade ahead of every form; wS = 0: none
         int wS = 0;
         double wsos[MEAS_MAX_WEIGHT_SECTIONS][5] = {};          // b0 b1 b2 a1 a2
@@ -830,6 +840,8 @@ static void meas_release(acme_batch::Measurement &M) {
     (void)be::dfree(M.d_wstate); (void)be::dfree(M.d_yw);
     (void)be::dfree(M.d_ens_member); (void)be::dfree(M.d_ens_off); (void)be::dfree(M.d_ens_acc);
     (void)be::dfree(M.d_hist_cnt); (void)be::dfree(M.d_hist_range);
+    (void)be::dfree(M.d_ev_lev); (void)be::dfree(M.d_ev_cnt); (void)be::dfree(M.d_ev_idx); (void)be::dfree(M.d_ev_ab);
+    (void)be::dfree(M.d_ev_state); (void)be::dfree(M.d_ev_prev);
     M = acme_batch::Measurement{};
 }
 
@@ -1550,6 +1562,12 @@ static int meas_step(acme_batch *b, const double *y, long long n, long long pitc
             memcpy(G.row, row, sizeof(G.row));
             HIPCHK(meas_hist_launch(G, st));
         }
+        if (M.events) { // ... and through the levels' automata, from where the chunk before left them
+            MeasEventsArgs G{y, M.d_ev_lev, M.d_ev_cnt, M.d_ev_idx, M.d_ev_ab, M.d_ev_state, M.d_ev_prev, b->N, len, pitch, s - M.pos,
+                             s - M.start, M.ev_C, M.ev_E, A.ny, M.nrows, {}};
+            memcpy(G.row, row, sizeof(G.row));
+            HIPCHK(meas_events_launch(G, st));
+        }
     }
     M.pos += n;
     return ACME_OK;
@@ -2258,6 +2276,10 @@ static int meas_zero(acme_batch *b) {
         HIPCHK(meas_hist_zero(M.d_hist_cnt, P * (size_t)(M.hist_B + 3)));
         HIPCHK(be::device_sync());
     }
+    if (M.events) {     // the counters, the slots and the carries (C, E and the levels stay)
+        HIPCHK(meas_events_zero(M.d_ev_cnt, M.d_ev_idx, M.d_ev_ab, M.d_ev_state, M.d_ev_prev, P, M.ev_C, M.ev_E));
+        HIPCHK(be::device_sync());
+    }
     if (M.wS) {         // the sections' states (the coefficients stay)
         HIPCHK(meas_weight_zero(M.d_wstate, P * 2 * (size_t)M.wS));
         HIPCHK(be::device_sync());
@@ -2437,6 +2459,7 @@ int acme_batch_set_measurement_series(acme_batch *b, long long win, long long ho
     if (M.target) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a target (a target per window is not supported)");
     if (M.ens) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has an ensemble (an ensemble per window is not supported)");
     if (M.hist) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has a histogram (a histogram per window is not supported)");
+    if (M.events) return fail(ACME_ERR_UNSUPPORTED, "measurement series: the measurement has events (events per window are not supported)");
     if (M.length != 0) return fail(ACME_ERR_INVALID, "measurement series: the armed measurement's length must be 0 (the series sets the windows)");
     if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement series: samples have been fed since arming (arm or reset the measurement first)");
     if (win < 1) return fail(ACME_ERR_INVALID, "measurement series: win must be >= 1");
@@ -2980,6 +3003,75 @@ int acme_batch_get_measurement_histogram(acme_batch *b, long long *counts, doubl
     if (range && !M.hist_range.empty()) memcpy(range, M.hist_range.data(), sizeof(double) * M.hist_range.size());
     const size_t n = (size_t)b->N * M.nrows * (size_t)(M.hist_B + 3);
     if (counts && n) HIPCHK(be::copy_d2h(counts, M.d_hist_cnt, sizeof(long long) * n));     // (the counters' layout is the result's)
+    return ACME_OK;
+}
+
+int acme_batch_set_measurement_events(acme_batch *b, int C, const double *lo, const double *hi, int E) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    acme_batch::Measurement &M = b->meas;
+    if (!M.on) return fail(ACME_ERR_INVALID, "measurement events: no measurement is armed");
+    if (M.W) return fail(ACME_ERR_UNSUPPORTED, "measurement events: the measurement has a series of windows (events per window are not supported)");
+    if (M.pos != 0) return fail(ACME_ERR_INVALID, "measurement events: samples have been fed since arming (arm or reset the measurement first)");
+    if (C < 1 || C > MEAS_MAX_EVENT_LEVELS)
+        return fail(ACME_ERR_INVALID, "measurement events: C is outside 1 ... " + std::to_string(MEAS_MAX_EVENT_LEVELS));
+    if (E < 0 || E > MEAS_MAX_EVENT_SLOTS)
+        return fail(ACME_ERR_INVALID, "measurement events: E is outside 0 ... " + std::to_string(MEAS_MAX_EVENT_SLOTS));
+    if (!lo) return fail(ACME_ERR_INVALID, "measurement events: lo is NULL");
+    if (!hi) return fail(ACME_ERR_INVALID, "measurement events: hi is NULL");
+    const long long PR = b->N * (long long)M.nrows;
+    if (PR > 0 && (long long)C * (E + 1) > MEAS_MAX_EVENTS / PR)
+        return fail(ACME_ERR_INVALID, "measurement events: N nrows C (E + 1) exceeds " + std::to_string(MEAS_MAX_EVENTS));
+    const size_t CN = (size_t)C * (size_t)b->N;
+    for (int c = 0; c < C; ++c)
+        for (long long i = 0; i < b->N; ++i) {
+            const double l = lo[c * b->N + i], h = hi[c * b->N + i];
+            const std::string at = " of level " + std::to_string(c) + ", instance " + std::to_string(i);
+            if (!std::isfinite(l)) return fail(ACME_ERR_INVALID, "measurement events: lo" + at + " is not finite");
+            if (!std::isfinite(h)) return fail(ACME_ERR_INVALID, "measurement events: hi" + at + " is not finite");
+            if (l > h) return fail(ACME_ERR_INVALID, "measurement events: lo > hi" + at);
+        }
+    std::vector<double> lev(2 * CN);
+    if (CN) { memcpy(lev.data(), lo, sizeof(double) * CN); memcpy(lev.data() + CN, hi, sizeof(double) * CN); }
+    const size_t tri = (size_t)PR * (size_t)C, rec = tri * 2 * (size_t)(E + 1);
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    (void)be::dfree(M.d_ev_lev); (void)be::dfree(M.d_ev_cnt); (void)be::dfree(M.d_ev_idx); (void)be::dfree(M.d_ev_ab);    // (events set again replace the earlier ones)
+    (void)be::dfree(M.d_ev_state); (void)be::dfree(M.d_ev_prev);
+    M.d_ev_lev = M.d_ev_ab = M.d_ev_prev = nullptr;
+    M.d_ev_cnt = M.d_ev_idx = nullptr;
+    M.d_ev_state = nullptr;
+    M.events = false;
+    HIPCHK(be::dmalloc((void **)&M.d_ev_lev, sizeof(double) * std::max<size_t>(lev.size(), 1)));
+    HIPCHK(be::dmalloc((void **)&M.d_ev_cnt, sizeof(long long) * std::max<size_t>(tri * 5, 1)));
+    HIPCHK(be::dmalloc((void **)&M.d_ev_idx, sizeof(long long) * std::max<size_t>(rec, 1)));
+    HIPCHK(be::dmalloc((void **)&M.d_ev_ab, sizeof(double) * std::max<size_t>(rec * 2, 1)));
+    HIPCHK(be::dmalloc((void **)&M.d_ev_state, sizeof(int) * std::max<size_t>(tri, 1)));
+    HIPCHK(be::dmalloc((void **)&M.d_ev_prev, sizeof(double) * std::max<size_t>((size_t)PR, 1)));
+    if (!lev.empty()) HIPCHK(be::copy_h2d(M.d_ev_lev, lev.data(), sizeof(double) * lev.size()));
+    HIPCHK(meas_events_zero(M.d_ev_cnt, M.d_ev_idx, M.d_ev_ab, M.d_ev_state, M.d_ev_prev, (size_t)PR, C, E));
+    HIPCHK(be::device_sync());
+    M.ev_lev = std::move(lev);
+    M.ev_C = C;
+    M.ev_E = E;
+    M.events = true;
+    return ACME_OK;
+}
+
+int acme_batch_get_measurement_events(acme_batch *b, long long *counts, long long *idx, double *ab, long long *count) {
+    join_worker(b);
+    if (!b) return fail(ACME_ERR_INVALID, "null batch");
+    const acme_batch::Measurement &M = b->meas;
+    if (!M.on || !M.events) return fail(ACME_ERR_INVALID, "no measurement events are set");
+    ON_DEVICE(b);
+    HIPCHK(be::device_sync());
+    const long long end = M.length ? M.start + M.length : LLONG_MAX;
+    const long long cnt = (M.pos < end ? M.pos : end) - M.start;
+    if (count) *count = cnt > 0 ? cnt : 0;
+    const size_t tri = (size_t)b->N * M.nrows * (size_t)M.ev_C, rec = tri * 2 * (size_t)(M.ev_E + 1);     // (the device's layout is the result's)
+    if (counts && tri) HIPCHK(be::copy_d2h(counts, M.d_ev_cnt, sizeof(long long) * tri * 5));
+    if (idx && rec) HIPCHK(be::copy_d2h(idx, M.d_ev_idx, sizeof(long long) * rec));
+    if (ab && rec) HIPCHK(be::copy_d2h(ab, M.d_ev_ab, sizeof(double) * rec * 2));
     return ACME_OK;
 }
 

@@ -116,6 +116,14 @@
 // own 32-bit counters, runs of equal counters among neighbouring lanes aggregated first, then a plain add of the non-zero
 // ones into global memory; the pairs of a block follow from B (meas_hist_waves); the emulator walks meas_hist_chain.
 //
+// EVENTS (acme_batch_set_measurement_events): the one form that says WHEN -- per (instance, row, level) a state UNKNOWN / LOW /
+// HIGH that v >= hi and v <= lo move (a comparator at lo == hi, a Schmitt trigger at lo < hi), five integer counters (RISE,
+// FALL and the samples after which the state is HIGH, LOW, UNKNOWN), the first E events of either direction and the last one
+// as (m, v[m - 1], v[m]), the values copied, and the state and the last value carried from chunk to chunk.  Comparisons and
+// integers only: the host forms the sub-sample times.  One more kernel per chunk (acme_meas_events_kernel): one wave per pair,
+// rounds of 64 consecutive samples, two ballots per level and round and the 64-bit mask algebra of meas_events_masks, which
+// the non-HIP backend's mask walk shares; the emulator walks meas_events_chain, the contract's loop.
+//
 // The per-element functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with g++).
 #pragma once
@@ -525,6 +533,146 @@ ACME_HD inline void meas_hist_chain(const MeasHistArgs &A, long long p) {
         const double v = yp[t * A.ny];
         c[meas_hist_bin(A.mode == MEAS_HIST_ABS ? fabs(v) : v, lo, hi, s, A.B)] += 1;
     }
+}
+
+// events: every (instance, row, level) triple is a two-state automaton over the window's samples (the contract of
+// include/acme_hip.h); cnt is [n * nrows * C][5] (RISE, FALL, HIGH, LOW, UNKNOWN), idx [n * nrows * C][2][E + 1], ab
+// [n * nrows * C][2][E + 1][2] in the result's order, lev [2][C][n] (lo, then hi), state [n * nrows * C] and prev [n * nrows]
+// (the last window sample's value) the carries
+constexpr int MEAS_MAX_EVENT_LEVELS = 8, MEAS_MAX_EVENT_SLOTS = 16;
+constexpr long long MEAS_MAX_EVENTS = 1ll << 24;        // N nrows C (E + 1) records per direction at most
+constexpr int MEAS_EV_UNKNOWN = 0, MEAS_EV_LOW = 1, MEAS_EV_HIGH = 2;
+constexpr int MEAS_EVENTS_WAVES = 4;        // pairs (one wave each) per block
+constexpr int MEAS_EVENTS_AHEAD = 8;        // rounds whose loads a wave has in flight
+
+struct MeasEventsArgs {
+    const double *y;            // instance i, sample t, row r at y[(i * pitch + t0 + t) * ny + r]
+    const double *lev;          // [2][C][n]
+    long long *cnt, *idx;
+    double *ab;
+    int *state;
+    double *prev;
+    long long n, len, pitch, t0, m0;    // m0: the chunk's first sample is number m0 >= 0 of the window
+    int C, E, ny, nrows;
+    unsigned char row[64];      // the measured rows, ascending
+};
+
+// THE MASK ALGEBRA of one round of up to 64 consecutive samples, bit l = sample l: S1 the samples with v >= hi, S0 those with
+// !(v >= hi) && v <= lo, `valid` the round's samples (bits from 0 up, S0 and S1 inside them), `state` the state before bit 0.
+// The state after sample l is that of the highest set bit of S0 | S1 at or below l, the carried one if there is none -- the
+// carry chain of an ADDITION: generate S1, propagate ~(S0 | S1), carry in state == HIGH.  In x = ~S0 + S1 + carry-in the
+// carry INTO bit l is bit l of x ^ propagate: the samples that find the state HIGH; the same with S0 and S1 exchanged gives
+// those that find it LOW.  No loop, no floating point.
+struct MeasEventsMasks {
+    unsigned long long rise, fall, high, low, unknown;      // events AT a sample; the state AFTER a sample
+    int carry;                                              // the state after the last valid sample
+};
+ACME_HD inline MeasEventsMasks meas_events_masks(unsigned long long S0, unsigned long long S1, int state, unsigned long long valid) {
+    const unsigned long long keep = ~(S0 | S1);
+    // (LOW is 1 and HIGH 2: the carries in and the state out are the state's two bits)
+    const unsigned long long was_high = (~S0 + S1 + (unsigned long long)(state >> 1 & 1)) ^ keep;
+    const unsigned long long was_low = (~S1 + S0 + (unsigned long long)(state & 1)) ^ keep;
+    const unsigned long long high = S1 | (keep & was_high), low = S0 | (keep & was_low);
+    MeasEventsMasks K;
+    K.rise = was_low & S1;
+    K.fall = was_high & S0;
+    K.high = high & valid;
+    K.low = low & valid;
+    K.unknown = ~(high | low) & valid;
+    K.carry = (int)(high >> 63) << 1 | (int)(low >> 63);    // (keep above the valid bits hands the state up to bit 63)
+    return K;
+}
+
+// the record of one event of a direction that has had `before` events: one of the first E slots of idx [E + 1], ab [E + 1][2]
+// while there is room (slot E, the last event, is the caller's: a register on the device)
+ACME_HD inline void meas_events_slot(long long *idx, double *ab, int E, long long before, long long m, double a, double b) {
+    if (before < E) {
+        idx[before] = m;
+        ab[2 * before] = a;
+        ab[2 * before + 1] = b;
+    }
+}
+
+// one pair over the chunk, level after level, sample after sample: the contract's loop as it stands (the non-HIP backend's
+// default walk)
+inline void meas_events_chain(const MeasEventsArgs &A, long long p) {
+    const long long i = p / A.nrows;
+    const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    for (int c = 0; c < A.C; ++c) {
+        const long long q = p * A.C + c;
+        const double lo = A.lev[c * A.n + i], hi = A.lev[(A.C + c) * A.n + i];
+        long long *cnt = A.cnt + q * 5, *idx = A.idx + q * 2 * (A.E + 1);
+        double *ab = A.ab + q * 4 * (A.E + 1);
+        int state = A.state[q];
+        double before = A.prev[p];
+        for (long long t = 0; t < A.len; ++t) {
+            const double v = yp[t * A.ny];
+            const int next = v >= hi ? MEAS_EV_HIGH : v <= lo ? MEAS_EV_LOW : state;
+            const int d = state == MEAS_EV_LOW && next == MEAS_EV_HIGH ? 0 : state == MEAS_EV_HIGH && next == MEAS_EV_LOW ? 1 : -1;
+            if (d >= 0) {
+                long long *id = idx + d * (A.E + 1);
+                double *abd = ab + d * 2 * (A.E + 1);
+                meas_events_slot(id, abd, A.E, cnt[d], A.m0 + t, before, v);
+                id[A.E] = A.m0 + t;
+                abd[2 * A.E] = before;
+                abd[2 * A.E + 1] = v;
+                cnt[d] += 1;
+            }
+            cnt[next == MEAS_EV_HIGH ? 2 : next == MEAS_EV_LOW ? 3 : 4] += 1;
+            state = next;
+            before = v;
+        }
+        A.state[q] = state;
+    }
+    if (A.len > 0) A.prev[p] = yp[(A.len - 1) * A.ny];
+}
+
+// the same pair in ROUNDS of 64 samples through meas_events_masks and meas_events_slot, the two masks formed by a loop in
+// place of the device's ballots: the algebra acme_meas_events_kernel runs, for the non-HIP backend (ACME_EVENTS_WALK=mask)
+inline void meas_events_mask_walk(const MeasEventsArgs &A, long long p) {
+    const long long i = p / A.nrows;
+    const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    double carried = A.prev[p];
+    for (long long tb = 0; tb < A.len; tb += 64) {
+        const int nv = A.len - tb < 64 ? (int)(A.len - tb) : 64;
+        const unsigned long long valid = nv == 64 ? ~0ull : (1ull << nv) - 1;
+        for (int c = 0; c < A.C; ++c) {
+            const long long q = p * A.C + c;
+            const double lo = A.lev[c * A.n + i], hi = A.lev[(A.C + c) * A.n + i];
+            unsigned long long S0 = 0, S1 = 0;
+            for (int l = 0; l < nv; ++l) {
+                const double v = yp[(tb + l) * A.ny];
+                const bool ge = v >= hi;
+                S1 |= (unsigned long long)ge << l;
+                S0 |= (unsigned long long)(!ge && v <= lo) << l;
+            }
+            const MeasEventsMasks K = meas_events_masks(S0, S1, A.state[q], valid);
+            long long *cnt = A.cnt + q * 5;
+            for (int d = 0; d < 2; ++d) {
+                const unsigned long long ev = d ? K.fall : K.rise;
+                long long *id = A.idx + (q * 2 + d) * (A.E + 1);
+                double *abd = A.ab + (q * 2 + d) * 2 * (A.E + 1);
+                for (int l = 0; l < nv; ++l) {
+                    if (!(ev >> l & 1)) continue;
+                    const long long ord = cnt[d] + __builtin_popcountll(ev & ((1ull << l) - 1));    // events so far + those below
+                    const double a = l ? yp[(tb + l - 1) * A.ny] : carried, b = yp[(tb + l) * A.ny];
+                    meas_events_slot(id, abd, A.E, ord, A.m0 + tb + l, a, b);
+                    if (!(ev >> l >> 1)) {      // the round's last event of the direction
+                        id[A.E] = A.m0 + tb + l;
+                        abd[2 * A.E] = a;
+                        abd[2 * A.E + 1] = b;
+                    }
+                }
+                cnt[d] += __builtin_popcountll(ev);
+            }
+            cnt[2] += __builtin_popcountll(K.high);
+            cnt[3] += __builtin_popcountll(K.low);
+            cnt[4] += __builtin_popcountll(K.unknown);
+            A.state[q] = K.carry;
+        }
+        carried = yp[(tb + nv - 1) * A.ny];
+    }
+    if (A.len > 0) A.prev[p] = carried;
 }
 
 // weighting: the slice's n base-rate samples of every measured row through the cascade, the weighted samples packed
@@ -1631,7 +1779,143 @@ __global__ __launch_bounds__(64 * acme::MEAS_HIST_WAVES) void acme_meas_hist_ker
         }
     }
 }
+
+// events: ONE WAVE PER PAIR, MEAS_EVENTS_WAVES pairs a block; no LDS, no atomic, no barrier -- nobody else owns the pair.  The
+// chunk is walked in ROUNDS of 64 consecutive samples, lane l holding sample 64 j + l (a wave's load is 512 contiguous bytes at
+// ny = 1), MEAS_EVENTS_AHEAD rounds' loads in flight.  The loaded value stays in its register while the C levels are walked:
+// per level two compares straight into scalar masks (S1: v >= hi, S0: v <= lo and not S1, both inside the round's valid
+// lanes) and meas_events_masks, 64-bit scalar arithmetic -- not one floating-point operation beyond the comparisons.  What
+// belongs to LEVEL c lives in LANE c's registers and is read with v_readlane and written under lane == c, the lane index the
+// loop's counter: a loop over a run-time C with no register array indexed by it.  Per level THREE packed words: `pk`, the
+// state in bits 0 ... 1 with the chunk's HIGH count from bit 2 and its LOW count from bit 17 (a chunk has at most 16 383
+// samples: the launcher refuses more); `ev`, the chunk's rises | falls << 16; `at`, the chunk sample of the last rise |
+// that of the last fall << 16 (0xffff: none).  A round without an event -- most -- costs the level two compares, five lane
+// reads and one select.  In a round with events the event lanes write their own slots while the direction has room
+// (the ordinal: the events so far + v_mbcnt of the mask below the lane), v[m - 1] being the lane below (DPP wave_shr:1, lane
+// 0 taking the previous round's last value or the carried one).  The last event of a direction is only a POSITION until the
+// chunk's end; lane c then reads its two values back from y (the chunk's first sample has the carried value below it) and
+// stores the last-event slot, the counters, the state and, lane 0, the last value with plain vector stores.
+__device__ inline double acme_meas_ev_readlane(double x, int l) {
+    const int lo = __builtin_amdgcn_readlane(__double2loint(x), l), hi = __builtin_amdgcn_readlane(__double2hiint(x), l);
+    return __hiloint2double(hi, lo);
+}
+__device__ inline double acme_meas_ev_below(double v, double first) {      // the lane below's v; lane 0: `first`
+    const int lo = __builtin_amdgcn_update_dpp(__double2loint(first), __double2loint(v), 0x138, 0xf, 0xf, false);    // wave_shr:1
+    const int hi = __builtin_amdgcn_update_dpp(__double2hiint(first), __double2hiint(v), 0x138, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+__global__ __launch_bounds__(64 * acme::MEAS_EVENTS_WAVES) void acme_meas_events_kernel(acme::MeasEventsArgs A) {
+    using namespace acme;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), C = A.C, E = A.E;
+    const long long p = (long long)blockIdx.x * MEAS_EVENTS_WAVES + wave;
+    if (p >= A.n * A.nrows) return;                     // (wave-uniform)
+    const long long i = p / A.nrows;
+    const double *yp = A.y + (i * A.pitch + A.t0) * A.ny + A.row[p - i * A.nrows];
+    const bool mine = lane < C;                         // lane c keeps level c
+    const long long q = p * C + (mine ? lane : 0);
+    long long *cq = A.cnt + q * 5, *iq = A.idx + q * 2 * (E + 1);
+    double *aq = A.ab + q * 4 * (E + 1);
+    double lo = 0.0, hi = 0.0;
+    long long base[2] = {0, 0};
+    int pk = MEAS_EV_UNKNOWN, ev = 0, at = -1, room = 0;    // room: the free slots at the chunk's start, rises | falls << 16
+    if (mine) {
+        lo = A.lev[lane * A.n + i];
+        hi = A.lev[(C + lane) * A.n + i];
+        pk = A.state[q];
+        base[0] = cq[0];
+        base[1] = cq[1];
+        room = (base[0] < E ? E - (int)base[0] : 0) | (base[1] < E ? E - (int)base[1] : 0) << 16;
+    }
+    const double carried0 = A.prev[p];
+    double carried = carried0;
+    for (long long tb = 0; tb < A.len; tb += 64 * MEAS_EVENTS_AHEAD) {
+        double v[MEAS_EVENTS_AHEAD];
+#pragma unroll
+        for (int u = 0; u < MEAS_EVENTS_AHEAD; ++u) {   // the loads are in flight together
+            const long long t = tb + 64 * u + lane;
+            v[u] = t < A.len ? yp[t * A.ny] : 0.0;
+        }
+#pragma unroll
+        for (int u = 0; u < MEAS_EVENTS_AHEAD; ++u) {
+            const int r0 = (int)tb + 64 * u;
+            if (r0 < A.len) {                           // (wave-uniform)
+                const int nv = A.len - r0 < 64 ? (int)(A.len - r0) : 64;
+                const unsigned long long valid = nv == 64 ? ~0ull : (1ull << nv) - 1;
+                for (int c = 0; c < C; ++c) {
+                    const double l = acme_meas_ev_readlane(lo, c), h = acme_meas_ev_readlane(hi, c);
+                    const unsigned long long S1 = __builtin_amdgcn_ballot_w64(v[u] >= h) & valid;
+                    const unsigned long long S0 = __builtin_amdgcn_ballot_w64(v[u] <= l) & valid & ~S1;
+                    const int w = __builtin_amdgcn_readlane(pk, c);
+                    const MeasEventsMasks K = meas_events_masks(S0, S1, w & 3, valid);
+                    const bool me = lane == c;
+                    pk = me ? (w & ~3) + (__builtin_popcountll(K.high) << 2) + (__builtin_popcountll(K.low) << 17) + K.carry : pk;
+                    if (K.rise | K.fall) {              // (wave-uniform; most rounds have no event)
+                        const int done = __builtin_amdgcn_readlane(ev, c), rm = __builtin_amdgcn_readlane(room, c);
+                        int where = __builtin_amdgcn_readlane(at, c);
+#pragma unroll
+                        for (int d = 0; d < 2; ++d) {
+                            const unsigned long long M = d ? K.fall : K.rise;
+                            if (!M) continue;
+                            const int dn = done >> 16 * d & 0xffff, free_ = rm >> 16 * d & 0xffff;
+                            if (dn < free_) {           // the direction has room: the event lanes write their slots
+                                const double a = acme_meas_ev_below(v[u], carried);
+                                const int ord = dn + (int)__builtin_amdgcn_mbcnt_hi((unsigned int)(M >> 32), __builtin_amdgcn_mbcnt_lo((unsigned int)M, 0u));
+                                if ((M >> lane & 1) && ord < free_) {
+                                    const long long rec = ((p * C + c) * 2 + d) * (E + 1);
+                                    meas_events_slot(A.idx + rec, A.ab + rec * 2, E, (long long)(E - free_) + ord, A.m0 + r0 + lane, a, v[u]);
+                                }
+                            }
+                            const int top = r0 + 63 - __builtin_clzll(M);   // the round's last event of the direction
+                            where = d ? (where & 0xffff) | top << 16 : (where & ~0xffff) | top;
+                        }
+                        at = me ? where : at;
+                        ev = me ? done + __builtin_popcountll(K.rise) + (__builtin_popcountll(K.fall) << 16) : ev;
+                    }
+                }
+                carried = acme_meas_ev_readlane(v[u], nv - 1);
+            }
+        }
+    }
+    if (mine) {
+        const long long nh = pk >> 2 & 0x7fff, nl = pk >> 17 & 0x7fff;
+        cq[0] = base[0] + (ev & 0xffff);
+        cq[1] = base[1] + (ev >> 16 & 0xffff);
+        cq[2] += nh;
+        cq[3] += nl;
+        cq[4] += A.len - nh - nl;
+        A.state[q] = pk & 3;
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            const int t = at >> 16 * d & 0xffff;
+            if (t != 0xffff) {                          // the direction's last event of the chunk: its two values, read back
+                iq[d * (E + 1) + E] = A.m0 + t;
+                aq[(d * (E + 1) + E) * 2] = t ? yp[(long long)(t - 1) * A.ny] : carried0;
+                aq[(d * (E + 1) + E) * 2 + 1] = yp[(long long)t * A.ny];
+            }
+        }
+    }
+    if (lane == 0) A.prev[p] = carried;
+}
 namespace acme {
+inline int meas_events_launch(const MeasEventsArgs &A, hipStream_t st) {
+    const long long pairs = A.n * A.nrows;
+    if (pairs <= 0 || A.len <= 0) return 0;
+    if (A.len > 16383) return (int)hipErrorInvalidValue;    // (the kernel's packed words; a chunk is MEAS_CHUNK at most)
+    const unsigned blocks = (unsigned)((pairs + MEAS_EVENTS_WAVES - 1) / MEAS_EVENTS_WAVES);
+    hipLaunchKernelGGL(acme_meas_events_kernel, dim3(blocks), dim3(64 * MEAS_EVENTS_WAVES), 0, st, A);
+    return (int)hipGetLastError();
+}
+// counters 0, slots (-1, 0.0, 0.0), states UNKNOWN, the last values 0.0
+inline int meas_events_zero(long long *cnt, long long *idx, double *ab, int *state, double *prev, size_t pairs, int C, int E) {
+    const size_t tri = pairs * (size_t)C, rec = tri * 2 * (size_t)(E + 1);
+    if (!tri) return 0;
+    int rc = (int)hipMemset(cnt, 0, sizeof(long long) * tri * 5);
+    if (!rc) rc = (int)hipMemset(idx, 0xff, sizeof(long long) * rec);
+    if (!rc) rc = (int)hipMemset(ab, 0, sizeof(double) * rec * 2);
+    if (!rc) rc = (int)hipMemset(state, 0, sizeof(int) * tri);
+    if (!rc) rc = (int)hipMemset(prev, 0, sizeof(double) * pairs);
+    return rc;
+}
 // the pairs of a block: as many waves as keep the block's counters within MEAS_HIST_LDS bytes, MEAS_HIST_WAVES at most
 inline int meas_hist_waves(int B) {
     const int w = MEAS_HIST_LDS / ((B + 3) * (int)sizeof(unsigned int));
@@ -1937,6 +2221,26 @@ inline int meas_hist_launch(const MeasHistArgs &A, void *) {
 }
 inline int meas_hist_zero(long long *cnt, size_t count) {
     std::fill(cnt, cnt + count, 0ll);
+    return 0;
+}
+// the contract's sequential loop unless ACME_EVENTS_WALK=mask in the environment: then the rounds of 64 through the mask
+// algebra the device kernel runs (an unsupported test hook, like ACME_HIST_AGG)
+inline int meas_events_launch(const MeasEventsArgs &A, void *) {
+    const char *e = getenv("ACME_EVENTS_WALK");
+    const bool mask = e && e[0] == 'm';
+    for (long long p = 0; p < A.n * A.nrows; ++p) {
+        if (mask) meas_events_mask_walk(A, p);
+        else meas_events_chain(A, p);
+    }
+    return 0;
+}
+inline int meas_events_zero(long long *cnt, long long *idx, double *ab, int *state, double *prev, size_t pairs, int C, int E) {
+    const size_t tri = pairs * (size_t)C, rec = tri * 2 * (size_t)(E + 1);
+    std::fill(cnt, cnt + tri * 5, 0ll);
+    std::fill(idx, idx + rec, -1ll);
+    std::fill(ab, ab + rec * 2, 0.0);
+    std::fill(state, state + tri, (int)MEAS_EV_UNKNOWN);
+    std::fill(prev, prev + pairs, 0.0);
     return 0;
 }
 inline int meas_fold_launch(const MeasFoldArgs &A, void *) {

@@ -75,6 +75,7 @@ ABI_SYMBOLS = [
     "acme_batch_set_measurement_weighting", "acme_batch_get_measurement_weighting",
     "acme_batch_set_measurement_ensemble", "acme_batch_get_measurement_ensemble",
     "acme_batch_set_measurement_histogram", "acme_batch_get_measurement_histogram",
+    "acme_batch_set_measurement_events", "acme_batch_get_measurement_events",
 ]
 
 SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE, SOURCE_NOISE = 1, 2, 3, 4, 5
@@ -87,6 +88,9 @@ MAX_ENSEMBLE = 16777216
 HIST_SIGNED, HIST_ABS = 0, 1
 MAX_HIST_BINS = 4096
 MAX_HISTOGRAM = 268435456
+MAX_EVENT_LEVELS, MAX_EVENT_SLOTS = 8, 16
+MAX_EVENTS = 16777216
+EVENT_RISE, EVENT_FALL, EVENT_HIGH, EVENT_LOW, EVENT_UNKNOWN = 0, 1, 2, 3, 4
 _SOURCE_KINDS = {"const": SOURCE_CONST, "sine": SOURCE_SINE, "table": SOURCE_TABLE, "multisine": SOURCE_MULTISINE, "noise": SOURCE_NOISE,
                  SOURCE_CONST: SOURCE_CONST, SOURCE_SINE: SOURCE_SINE, SOURCE_TABLE: SOURCE_TABLE, SOURCE_MULTISINE: SOURCE_MULTISINE,
                  SOURCE_NOISE: SOURCE_NOISE}
@@ -225,6 +229,8 @@ class Library:
         L.acme_batch_get_measurement_ensemble.argtypes = [vp, dp, lp, lp, lp]
         L.acme_batch_set_measurement_histogram.argtypes = [vp, C.c_int, C.c_int, C.c_double, C.c_double, dp, dp]
         L.acme_batch_get_measurement_histogram.argtypes = [vp, lp, dp, lp]
+        L.acme_batch_set_measurement_events.argtypes = [vp, C.c_int, dp, dp, C.c_int]
+        L.acme_batch_get_measurement_events.argtypes = [vp, lp, lp, dp, lp]
         L.acme_batch_set_measurement_weighting.argtypes = [vp, dp, C.c_int]
         L.acme_batch_get_measurement_weighting.argtypes = [vp, dp, C.POINTER(C.c_int)]
 
@@ -733,6 +739,86 @@ class MeasurementHistogram:
         return cls(cat("counts"), cat("under"), cat("over"), cat("nan"), a.count, cat("lo"), cat("hi"), cat("scale"), a.mode, a.rows)
 
 
+class MeasurementEvents:
+    """What ``ModelRunner.measurement_events()`` returns: the level crossings of every (instance, measured row, level).  The
+    raw arrays are the library's: ``counts`` (N, nrows, C, 5) int64 -- RISE, FALL, then the samples after which the state is
+    HIGH, LOW, UNKNOWN, the last three summing to ``count`` --, ``idx`` (N, nrows, C, 2, E + 1) int64 the window samples ``m``
+    of the recorded events (direction 0: rises, 1: falls; slots 0 ... E - 1 the first E, slot E the last so far; -1: empty) and
+    ``ab`` (N, nrows, C, 2, E + 1, 2) their ``v[m - 1]`` and ``v[m]`` bit for bit; ``lo``, ``hi`` (C, N) the levels; ``rows`` the
+    measured output rows.  The helpers form the times on the host, in window samples from ``start``:
+    ``t = (m - 1) + (thr - a) / (b - a)`` with ``thr = hi`` for a rise and ``lo`` for a fall, ``t = m`` where ``a`` is NaN."""
+
+    def __init__(self, counts, idx, ab, count, lo, hi, rows):
+        self.counts, self.idx, self.ab = counts, idx, ab
+        self.count, self.rows = int(count), tuple(rows)
+        self.lo, self.hi = (np.asarray(a, dtype=np.float64) for a in (lo, hi))
+
+    levels = property(lambda self: self.counts.shape[2])
+    slots = property(lambda self: self.idx.shape[-1] - 1)
+    rises = property(lambda self: self.counts[..., EVENT_RISE])
+    falls = property(lambda self: self.counts[..., EVENT_FALL])
+    high = property(lambda self: self.counts[..., EVENT_HIGH])
+    low = property(lambda self: self.counts[..., EVENT_LOW])
+    unknown = property(lambda self: self.counts[..., EVENT_UNKNOWN])
+
+    @staticmethod
+    def _direction(direction):
+        d = {"rise": EVENT_RISE, "fall": EVENT_FALL, EVENT_RISE: EVENT_RISE, EVENT_FALL: EVENT_FALL}.get(direction)
+        if d is None:
+            raise ValueError(f"direction must be 'rise' or 'fall', not {direction!r}")
+        return d
+
+    def times(self, direction, level=0):
+        """``(t, t_last)``: the sub-sample times of the first E events of ``direction`` (``"rise"`` or ``"fall"``) at
+        ``level``, (N, nrows, E), NaN where a slot is empty, and the last event's time (N, nrows), NaN where there was none"""
+        d = self._direction(direction)
+        m = self.idx[:, :, level, d, :].astype(np.float64)
+        a, b = self.ab[:, :, level, d, :, 0], self.ab[:, :, level, d, :, 1]
+        thr = (self.hi if d == EVENT_RISE else self.lo)[level][:, None, None]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            t = np.where(np.isnan(a), m, (m - 1.0) + (thr - a) / (b - a))
+        t = np.where(self.idx[:, :, level, d, :] < 0, np.nan, t)
+        return t[..., :-1], t[..., -1]
+
+    def frequency(self, fs, level=0):
+        """the frequency of an oscillating row from its rises at ``level`` (N, nrows): ``(n - 1) / (t_last - t_first) fs``, NaN
+        with fewer than two rises (or with ``slots == 0``: the first rise is not recorded)"""
+        t, last = self.times("rise", level)
+        n = self.rises[:, :, level].astype(np.float64)
+        if t.shape[-1] == 0:
+            return np.full(n.shape, np.nan)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(n >= 2, (n - 1.0) / (last - t[..., 0]) * fs, np.nan)
+
+    def duty(self, level=0):
+        """the share of the decided samples the row spends HIGH at ``level`` (N, nrows): ``HIGH / (HIGH + LOW)``"""
+        h, l = self.high[:, :, level].astype(np.float64), self.low[:, :, level].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return h / (h + l)
+
+    def transition_time(self, level_a, level_b, direction="rise"):
+        """the first event of ``direction`` at ``level_b`` minus the first at ``level_a``, in samples (N, nrows): the rise
+        time between a 10 % and a 90 % level; NaN where either has none (needs ``slots >= 1``)"""
+        ta, tb = self.times(direction, level_a)[0], self.times(direction, level_b)[0]
+        if ta.shape[-1] == 0:
+            return np.full(ta.shape[:2], np.nan)
+        return tb[..., 0] - ta[..., 0]
+
+    def last_time(self, level=0):
+        """the later of the last rise and the last fall at ``level`` (N, nrows), NaN where there was neither: with two levels
+        that bracket the final value, the settling time out of the band"""
+        return np.fmax(self.times("rise", level)[1], self.times("fall", level)[1])
+
+    @classmethod
+    def concatenate(cls, parts):
+        """several batches' results (the shards of ``MultiDeviceRunner``) as one, along the instances"""
+        a = parts[0]
+        if any((p.count, p.rows, p.levels, p.slots) != (a.count, a.rows, a.levels, a.slots) for p in parts):
+            raise ValueError("the shards' events differ in their sample counts, measured rows, levels or slots")
+        cat = lambda k, axis=0: np.concatenate([getattr(p, k) for p in parts], axis=axis)
+        return cls(cat("counts"), cat("idx"), cat("ab"), a.count, cat("lo", 1), cat("hi", 1), a.rows)
+
+
 class MeasurementWeighting:
     """What ``ModelRunner.measurement_weighting()`` returns, and what ``set_measurement_weighting`` accepts: a cascade of
     second-order sections, ``sos`` (S, 5) with the rows ``b0 b1 b2 a1 a2`` of
@@ -979,6 +1065,7 @@ class ModelRunner:
         self._weighting = False         # a weighting is set on the armed measurement
         self._ensemble = None           # (G, stride, E) of the ensemble set on the armed measurement
         self._histogram = None          # (B, mode) of the histogram set on the armed measurement
+        self._events = None             # (C, E, lo, hi) of the events set on the armed measurement
         self._length = 0                # the armed measurement's window length (0: unbounded)
         self._sources = {}              # input row -> kind, while the row has a source
         self._sine = {}                 # input row -> (f_den, f_num as armed) of its sine source
@@ -1078,6 +1165,7 @@ class ModelRunner:
         self._weighting = False
         self._ensemble = None
         self._histogram = None
+        self._events = None
         return self
 
     def set_measurement_bins(self, coef, start=0, length=0, rows=None, f_den=None, f_num=None, tones_from_source=None):
@@ -1120,6 +1208,7 @@ class ModelRunner:
         self._weighting = False
         self._ensemble = None
         self._histogram = None
+        self._events = None
         return self
 
     def measurement_plan(self):
@@ -1147,6 +1236,7 @@ class ModelRunner:
         self._weighting = False
         self._ensemble = None
         self._histogram = None
+        self._events = None
         return self
 
     def set_measurement_series(self, win, hop=None, windows=1):
@@ -1440,6 +1530,51 @@ class ModelRunner:
                                                                        C.byref(count)))
         return MeasurementHistogram(raw[..., 1:B + 1].copy(), raw[..., 0].copy(), raw[..., B + 1].copy(), raw[..., B + 2].copy(),
                                     count.value, rng[:, 0].copy(), rng[:, 1].copy(), rng[:, 2].copy(), mode, rows)
+
+    def set_measurement_events(self, levels=None, hysteresis=0.0, slots=8, lo=None, hi=None):
+        """Record when every measured row crosses levels (``acme_batch_set_measurement_events``): rise and fall times, delays,
+        settling, frequency from zero crossings, duty cycle, chatter across a trip level, with no y stored.  ``levels``: a
+        scalar, C values or (C, N) values, one row per level; each becomes the band ``level -+ hysteresis / 2`` (0.0: a plain
+        comparator).  Or ``lo=`` and ``hi=`` explicitly, C or (C, N) values each, ``lo <= hi``.  ``slots``: the first events
+        recorded per direction (the last one always is).  Needs an armed measurement that has not been fed yet; not together
+        with a series; ``measurement_events`` reads it."""
+        if self._meas is None:
+            raise AcmeError("no measurement is armed")
+        if (levels is None) == (lo is None and hi is None) or (lo is None) != (hi is None):
+            raise ValueError("give either levels (with a hysteresis) or both lo and hi")
+        if not hysteresis >= 0.0:
+            raise ValueError("hysteresis must be >= 0")
+
+        def full(a, name):
+            a = np.asarray(a, dtype=np.float64)
+            a = a.reshape(1, 1) if a.ndim == 0 else a[:, None] if a.ndim == 1 else a
+            if a.ndim != 2 or a.shape[1] not in (1, self.n):
+                raise DimensionMismatch(f"{name} needs C or (C, {self.n}) values")
+            return np.ascontiguousarray(np.broadcast_to(a, (a.shape[0], self.n)))
+        if levels is not None:
+            mid = full(levels, "levels")
+            la, ha = mid - 0.5 * hysteresis, mid + 0.5 * hysteresis
+        else:
+            la, ha = full(lo, "lo"), full(hi, "hi")
+            if la.shape != ha.shape:
+                raise DimensionMismatch("lo and hi need the same number of levels")
+        self.lib.check(self.lib.L.acme_batch_set_measurement_events(self.h, la.shape[0], _dp(la), _dp(ha), int(slots)))
+        self._events = (la.shape[0], int(slots), la, ha)
+        return self
+
+    def measurement_events(self):
+        """the events so far (``acme_batch_get_measurement_events``): a ``MeasurementEvents``"""
+        if self._meas is None or self._events is None:
+            raise AcmeError("no measurement events are set")
+        rows = self._meas[1]
+        nC, E, la, ha = self._events
+        lp = C.POINTER(C.c_longlong)
+        counts = np.empty((self.n, len(rows), nC, 5), dtype=np.int64)
+        idx = np.empty((self.n, len(rows), nC, 2, E + 1), dtype=np.int64)
+        ab, count = np.empty((self.n, len(rows), nC, 2, E + 1, 2)), C.c_longlong(0)
+        self.lib.check(self.lib.L.acme_batch_get_measurement_events(self.h, counts.ctypes.data_as(lp), idx.ctypes.data_as(lp), _dp(ab),
+                                                                    C.byref(count)))
+        return MeasurementEvents(counts, idx, ab, count.value, la.copy(), ha.copy(), rows)
 
     def reset_measurement(self):
         """zero the accumulators and restart the window's clock (``acme_batch_reset_measurement``)"""
@@ -2171,6 +2306,23 @@ class MultiDeviceRunner:
     def measurement_histogram(self):
         """the shards' ``MeasurementHistogram`` results, concatenated along the instances (nothing joins across shards)"""
         return MeasurementHistogram.concatenate([r.measurement_histogram() for r in self.runners if r is not None])
+
+    def set_measurement_events(self, levels=None, hysteresis=0.0, slots=8, lo=None, hi=None):
+        """``ModelRunner.set_measurement_events`` on every device's batch, (C, N) levels sliced over the devices' instances"""
+        def part(a, lo_, hi_):
+            if a is None or np.ndim(a) < 2:
+                return a
+            if np.shape(a)[1] not in (1, self.n):
+                raise DimensionMismatch(f"the levels need C or (C, {self.n}) values")
+            return a if np.shape(a)[1] == 1 else np.asarray(a)[:, lo_:hi_]
+        for r, (a, b) in zip(self.runners, self.ranges):
+            if r is not None:
+                r.set_measurement_events(part(levels, a, b), hysteresis, slots, part(lo, a, b), part(hi, a, b))
+        return self
+
+    def measurement_events(self):
+        """the shards' ``MeasurementEvents`` results, concatenated along the instances (nothing joins across shards)"""
+        return MeasurementEvents.concatenate([r.measurement_events() for r in self.runners if r is not None])
 
     def set_measurement_weighting(self, sos):
         """``ModelRunner.set_measurement_weighting`` on every device's batch: the same cascade everywhere"""

@@ -640,6 +640,68 @@ int acme_batch_set_measurement_histogram(acme_batch *b, int bins, int mode, doub
  * acme_batch_run_async and synchronises the device. */
 int acme_batch_get_measurement_histogram(acme_batch *b, long long *counts /* [N][nrows][B + 3] */,
                                          double *range /* [N][3]: lo_i, hi_i, s_i */, long long *count);
+/* EVENTS of the window: the armed measurement (any of the three forms, any start / length, bounded or not, no sample fed
+ * since arming or the last reset) also records WHEN the measured rows cross levels, per instance, measured row and level -- the
+ * `.measure TRIG / TARG / WHEN` questions of a circuit simulator: the rise and fall time of a step response between its 10 %
+ * and 90 % levels, the delay to a threshold, the settling time (the last time the output leaves a band), the frequency of an
+ * oscillating output from its zero crossings to a fraction of a sample, the duty cycle of a clipped or comparator output, how
+ * often a noisy output chatters across a trip level with a Schmitt hysteresis or without.  A few integers and sample pairs per
+ * (instance, row, level) in place of y [N][T][ny].
+ *   C        levels per instance, 1 ... ACME_MAX_EVENT_LEVELS
+ *   lo, hi   HOST arrays [C][N], copied by the call: level c of instance i at [c * N + i]; every value finite, lo <= hi.
+ *            lo == hi is a plain comparator, lo < hi a Schmitt trigger
+ *   E        the first events recorded per direction, 0 ... ACME_MAX_EVENT_SLOTS; N nrows C (E + 1) <= ACME_MAX_EVENTS
+ * Every triple (instance i, measured row r, level c) has a STATE, UNKNOWN, LOW or HIGH, UNKNOWN at the window's first sample.
+ * Window sample m counts from 0 at `start`; its value v is the value the other forms see (the weighted row behind a weighting,
+ * the base-rate row after the decimation of an oversampled batch).  Per sample:
+ *   if      (v >= hi) next = HIGH
+ *   else if (v <= lo) next = LOW
+ *   else              next = state            inside the band, or NaN: keep
+ *   RISE at m  iff state == LOW  and next == HIGH
+ *   FALL at m  iff state == HIGH and next == LOW
+ * Leaving UNKNOWN is no event: an event never falls on m = 0, and v[m - 1] exists for every event.  The device performs NO
+ * floating-point arithmetic, only comparisons.  Per triple it keeps
+ *   five 64-bit counters, in this order: RISE and FALL, the events; HIGH and LOW, the samples whose state AFTER the sample is
+ *            HIGH or LOW (a NaN sample counts in the state it keeps); UNKNOWN, the samples after which the state is still
+ *            unknown.  HIGH + LOW + UNKNOWN == count for every triple;
+ *   E + 1 event records per direction (0: rises, 1: falls): slots 0 ... E - 1 the first E events in time order, slot E the LAST
+ *            event so far (it equals slot n - 1 while the direction has had n <= E events).  A record is (m, a, b) = (the
+ *            window sample as a 64-bit integer, v[m - 1], v[m]), the values copied bit for bit; an empty slot is (-1, 0.0, 0.0).
+ *            The HOST forms the time to a fraction of a sample, t = (m - 1) + (thr - a) / (b - a) with thr = hi for a rise and
+ *            lo for a fall, t = m where a is NaN: no quotient has to be bit-exact anywhere;
+ *   the state and the last window sample's value, carried across chunks, slices and calls.
+ * Integers and copied values, so the result depends on nothing but the run's samples: T1 then T2 samples equal one run of
+ * T1 + T2, and chunk, slice and call boundaries, host or device memory, the entry point (acme_batch_run, _run_const,
+ * _run_async, _run_sources), the oversampling factor, a weighting beyond what it feeds as v and whether y is stored change
+ * none of its bits.  The measurement's own accumulators, plan, launches and getter are what they are without events, and so are
+ * those of a fold, a spectrum, a cross-spectrum, a target, a weighting, an ensemble and a histogram set beside them; events
+ * take one more kernel per chunk of the window.
+ * ACME_ERR_INVALID (the message names the argument, and the level and instance of an entry of lo / hi): no measurement armed,
+ * samples already fed, C outside 1 ... ACME_MAX_EVENT_LEVELS, E outside 0 ... ACME_MAX_EVENT_SLOTS, lo or hi NULL, a
+ * non-finite level, lo > hi, N nrows C (E + 1) beyond ACME_MAX_EVENTS (the product equal to it is accepted).
+ * ACME_ERR_UNSUPPORTED together with a series, whichever is set first.  Setting events again replaces the earlier ones.
+ * _reset_measurement zeroes the counters, empties the slots and returns the states to UNKNOWN; it keeps C, E and the levels.
+ * Arming any form or _clear_measurement removes the events; acme_batch_set_matrices carries them with the accumulators.  A batch
+ * without events launches, allocates and synchronises what it always did.
+ * Out of scope: levels per ROW (an instance's levels serve all its measured rows); events per window of a series; more than
+ * the first E and the last event of a direction -- count them, or use a longer E on a shorter window. */
+#define ACME_MAX_EVENT_LEVELS 8
+#define ACME_MAX_EVENT_SLOTS 16
+#define ACME_MAX_EVENTS 16777216            /* N nrows C (E + 1) records per direction at most */
+#define ACME_EVENT_RISE 0                   /* the counters of a triple, in the getter's order */
+#define ACME_EVENT_FALL 1
+#define ACME_EVENT_HIGH 2
+#define ACME_EVENT_LOW 3
+#define ACME_EVENT_UNKNOWN 4
+int acme_batch_set_measurement_events(acme_batch *b, int C, const double *lo /* host [C][N] */, const double *hi /* host [C][N] */,
+                                      int E);
+/* the events so far (each argument may be NULL): counts[N][nrows][C][5] -- RISE, FALL, HIGH, LOW, UNKNOWN --,
+ * idx[N][nrows][C][2][E + 1] the records' window samples m (rises, then falls; -1: empty), ab[N][nrows][C][2][E + 1][2] their
+ * v[m - 1] and v[m], *count the samples measured, as acme_batch_get_measurement counts them.  ACME_ERR_INVALID without events.
+ * Joins a pending acme_batch_run_async and synchronises the device. */
+int acme_batch_get_measurement_events(acme_batch *b, long long *counts /* [N][nrows][C][5] */,
+                                      long long *idx /* [N][nrows][C][2][E + 1] */, double *ab /* [N][nrows][C][2][E + 1][2] */,
+                                      long long *count);
 /* switch the measurement off (y = NULL is refused again) */
 int acme_batch_clear_measurement(acme_batch *b);
 /* zero the accumulators and restart the window's clock (the armed parameters stay) */

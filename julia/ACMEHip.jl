@@ -41,7 +41,7 @@ export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host
        set_measurement_fold!, measurement_fold, set_measurement_spectrum!, measurement_spectrum,
        set_measurement_cross!, measurement_cross, set_measurement_target!, measurement_target,
        set_measurement_weighting!, measurement_weighting, set_measurement_ensemble!, measurement_ensemble,
-       set_measurement_histogram!, measurement_histogram
+       set_measurement_histogram!, measurement_histogram, set_measurement_events!, measurement_events
 
 const lib = get(ENV, "ACME_HIP_LIB", "libacme_hip.so")
 
@@ -62,6 +62,10 @@ const ACME_MAX_ENSEMBLE = 16777216
 const ACME_HIST_SIGNED, ACME_HIST_ABS = Cint(0), Cint(1)
 const ACME_MAX_HIST_BINS = 4096
 const ACME_MAX_HISTOGRAM = 268435456
+const ACME_MAX_EVENT_LEVELS = 8
+const ACME_MAX_EVENT_SLOTS = 16
+const ACME_MAX_EVENTS = 16777216
+const ACME_EVENT_RISE, ACME_EVENT_FALL, ACME_EVENT_HIGH, ACME_EVENT_LOW, ACME_EVENT_UNKNOWN = Cint(0), Cint(1), Cint(2), Cint(3), Cint(4)
 const ACME_SOURCE_CONST, ACME_SOURCE_SINE, ACME_SOURCE_TABLE, ACME_SOURCE_MULTISINE = Cint(1), Cint(2), Cint(3), Cint(4)
 const ACME_SOURCE_NOISE = Cint(5)
 const ACME_NOISE_UNIFORM, ACME_NOISE_GAUSSIAN = Cint(0), Cint(1)
@@ -233,6 +237,7 @@ mutable struct BatchRunner
     cross::Int                        # nfft of the cross-spectrum set on the armed measurement (0: none)
     ensemble::Tuple{Int,Int}          # (G, stride) of the ensemble set on the armed measurement ((0, 0): none)
     histogram::Int                    # the bins B of the histogram set on the armed measurement (0: none)
+    events::Tuple{Int,Int}            # (C, E) of the events set on the armed measurement ((0, 0): none)
 end
 
 # @showprogress of run!(runner, y, u) (src/ACME.jl:587-604,653): the library reports after every time slice of a
@@ -251,7 +256,7 @@ function BatchRunner(model::DiscreteModel, n::Integer; device::Integer=-1,
     b = Ref{Ptr{Cvoid}}()
     check(ccall((:acme_batch_create, lib), Cint, (Ptr{Cvoid}, Clonglong, Ref{AcmeOptions}, Ref{Ptr{Cvoid}}),
                 mh.h, n, opts, b))
-    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress, nothing, Set{Int}(), 0, 0, (0, 0), 0)
+    r = BatchRunner(model, n, b[], mh, 0, Ref{Any}(nothing), showprogress, nothing, Set{Int}(), 0, 0, (0, 0), 0, (0, 0))
     finalizer(r -> ccall((:acme_batch_destroy, lib), Cvoid, (Ptr{Cvoid},), r.h), r)
     if showprogress
         cb = @cfunction(progress_trampoline, Cvoid, (Ptr{Cvoid}, Clonglong, Clonglong))
@@ -497,6 +502,7 @@ function set_measurement!(r::BatchRunner, spec::MeasureSpec)
     r.cross = 0
     r.ensemble = (0, 0)
     r.histogram = 0
+    r.events = (0, 0)
     return r
 end
 function set_measurement!(r::BatchRunner; f_den=nothing, f_num=nothing, kwargs...)
@@ -523,6 +529,7 @@ function set_measurement!(r::BatchRunner, spec::MeasureSpec, f_den::Int64, f_num
     r.cross = 0
     r.ensemble = (0, 0)
     r.histogram = 0
+    r.events = (0, 0)
     return r
 end
 
@@ -550,6 +557,7 @@ function set_measurement_bins!(r::BatchRunner, coef::Matrix{<:Integer}, f_den::I
     r.cross = 0
     r.ensemble = (0, 0)
     r.histogram = 0
+    r.events = (0, 0)
     return r
 end
 
@@ -579,6 +587,7 @@ function clear_measurement!(r::BatchRunner)
     r.cross = 0
     r.ensemble = (0, 0)
     r.histogram = 0
+    r.events = (0, 0)
     return r
 end
 
@@ -943,6 +952,50 @@ function measurement_histogram(r::BatchRunner)
                 (Ptr{Cvoid}, Ptr{Clonglong}, Ptr{Cdouble}, Ref{Clonglong}), r.h, raw, range, count))
     return (counts=raw[2:B + 1, :, :], under=raw[1, :, :], over=raw[B + 2, :, :], nan=raw[B + 3, :, :],
             lo=range[1, :], hi=range[2, :], scale=range[3, :], count=count[])
+end
+
+"""
+    set_measurement_events!(runner, lo, hi; slots=8)
+
+Record when every measured row crosses levels (`acme_batch_set_measurement_events`): `lo` and `hi` are `N x C` matrices (or
+vectors of `C` levels that serve every instance), level `c` of instance `i` the band `[lo[i, c], hi[i, c]]` -- `lo == hi` a plain
+comparator, `lo < hi` a Schmitt trigger; `slots` the first events recorded per direction.  Needs an armed measurement that has
+not been fed yet; not together with a series.
+"""
+function set_measurement_events!(r::BatchRunner, lo, hi; slots::Integer=8)
+    r.meas === nothing && error("no measurement is armed")
+    full(a) = a isa AbstractVector ? repeat(reshape(Float64.(a), 1, :), r.n, 1) : Matrix{Float64}(a)
+    l, h = full(lo), full(hi)                                        # N x C column-major: the ABI's [C][N]
+    size(l) == size(h) && size(l, 1) == r.n || throw(DimensionMismatch("lo and hi are N x C matrices, or vectors of C levels"))
+    nc = size(l, 2)
+    GC.@preserve l h check(ccall((:acme_batch_set_measurement_events, lib), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Cint), r.h, nc, pointer(l), pointer(h), slots))
+    r.events = (nc, Int(slots))
+    return r
+end
+
+"""
+    measurement_events(runner) -> (counts, idx, ab, count)
+
+The events so far (`acme_batch_get_measurement_events`), for the levels and slots that `set_measurement_events!` set (the runner
+keeps them and sizes the arrays): `counts` `5 x C x nrows x N` (RISE, FALL, HIGH, LOW, UNKNOWN), `idx` `(E + 1) x 2 x C x nrows x N`
+the window samples `m` of the first `E` and the last event of either direction (rises, then falls; -1: empty), `ab`
+`2 x (E + 1) x 2 x C x nrows x N` their `v[m - 1]` and `v[m]`, and `count`, the samples measured.  The time of an event to a
+fraction of a sample is `(m - 1) + (thr - a) / (b - a)` with `thr` the level's `hi` for a rise and `lo` for a fall.
+"""
+function measurement_events(r::BatchRunner)
+    spec = r.meas
+    nc, E = r.events
+    (spec === nothing || nc == 0) && error("no measurement events are set")
+    ny = ACME.ny(r.model)
+    nrows = spec.rows == 0 ? min(ny, 64) : count_ones(spec.rows)
+    counts = Array{Int64,4}(undef, 5, nc, nrows, r.n)                 # the ABI's [N][nrows][C][5]
+    idx = Array{Int64,5}(undef, E + 1, 2, nc, nrows, r.n)             # ... [N][nrows][C][2][E + 1]
+    ab = Array{Float64,6}(undef, 2, E + 1, 2, nc, nrows, r.n)         # ... and [N][nrows][C][2][E + 1][2]
+    count = Ref{Clonglong}(0)
+    check(ccall((:acme_batch_get_measurement_events, lib), Cint,
+                (Ptr{Cvoid}, Ptr{Clonglong}, Ptr{Clonglong}, Ptr{Cdouble}, Ref{Clonglong}), r.h, counts, idx, ab, count))
+    return (counts=counts, idx=idx, ab=ab, count=count[])
 end
 
 """
