@@ -285,6 +285,7 @@ static void src_release(acme_batch *b, int row) {
         if (R.kind == SRC_NONE) continue;
         (void)be::dfree(const_cast<double *>(R.amp)); (void)be::dfree(const_cast<double *>(R.off)); (void)be::dfree(const_cast<double *>(R.w));
         (void)be::dfree(const_cast<long long *>(R.fnum)); (void)be::dfree(const_cast<long long *>(R.phase));
+        (void)be::dfree(const_cast<long long *>(R.shape));
         R = SrcRow{};
         S.mask &= ~(1ull << r);
         S.cmask &= ~(1ull << r);
@@ -1982,9 +1983,10 @@ static int src_commit(acme_batch *b) {
     return ACME_OK;
 }
 // kind, den (SINE, MULTISINE: f_den; TABLE: P; NOISE: hold), the arrays of the kind (host arrays of N entries, w of P; NULL =
-// default; MULTISINE: f_num, phase and amp hold tones x N entries; NOISE: f_num holds the streams, tones the distribution)
+// default; MULTISINE: f_num, phase and amp hold tones x N entries; NOISE: f_num holds the streams, tones the distribution;
+// PULSE, BURST: shape holds 5 x N entries -- period, delay, rise, on, fall)
 static int set_source(acme_batch *b, int row, int kind, long long den, const long long *f_num, const long long *phase,
-                      const double *w, const double *amp, const double *offset, int tones = 1) {
+                      const double *w, const double *amp, const double *offset, int tones = 1, const long long *shape = nullptr) {
     join_worker(b);
     if (!b) return fail(ACME_ERR_INVALID, "null batch");
     const int nu = b->P.actual.nu;
@@ -2005,11 +2007,25 @@ static int set_source(acme_batch *b, int row, int kind, long long den, const lon
                     return fail(ACME_ERR_INVALID, "source: non-finite amp (tone " + std::to_string(k) + ", instance " + std::to_string(i) + ")");
             }
     }
-    if (kind == SRC_SINE) {
-        if (den <= 0 || den >= (1ll << 31)) return fail(ACME_ERR_INVALID, "sine source: f_den must be 1 ... 2^31 - 1");
+    if (kind == SRC_SINE || kind == SRC_BURST) {
+        const std::string what = kind == SRC_SINE ? "sine source" : "burst source";
+        if (den <= 0 || den >= (1ll << 31)) return fail(ACME_ERR_INVALID, what + ": f_den must be 1 ... 2^31 - 1");
         for (size_t i = 0; i < N; ++i)
             if ((f_num && (f_num[i] < 0 || f_num[i] >= den)) || (phase && (phase[i] < 0 || phase[i] >= den)))
-                return fail(ACME_ERR_INVALID, "sine source: f_num and phase must be 0 ... f_den - 1 (instance " + std::to_string(i) + ")");
+                return fail(ACME_ERR_INVALID, what + ": f_num and phase must be 0 ... f_den - 1 (instance " + std::to_string(i) + ")");
+    }
+    if (kind == SRC_PULSE || kind == SRC_BURST) {
+        const std::string what = kind == SRC_PULSE ? "pulse source" : "burst source";
+        if (!shape) return fail(ACME_ERR_INVALID, what + ": null shape");
+        for (size_t i = 0; i < N; ++i) {
+            const long long P = shape[i], delay = shape[N + i], rise = shape[2 * N + i], on = shape[3 * N + i], fall = shape[4 * N + i];
+            const std::string inst = " (instance " + std::to_string(i) + ")";
+            if (P < 1 || P >= (1ll << 31)) return fail(ACME_ERR_INVALID, what + ": period must be 1 ... 2^31 - 1" + inst);
+            if (delay < 0 || delay >= P) return fail(ACME_ERR_INVALID, what + ": delay must be 0 ... period - 1" + inst);
+            if (rise < 0 || on < 0 || fall < 0) return fail(ACME_ERR_INVALID, what + ": negative rise, on or fall" + inst);
+            if (rise > P || on > P || fall > P || rise + on + fall > P)
+                return fail(ACME_ERR_INVALID, what + ": rise + on + fall must not exceed the period" + inst);
+        }
     }
     if (kind == SRC_TABLE) {
         if (den < 1 || den > SRC_MAX_TABLE) return fail(ACME_ERR_INVALID, "table source: P must be 1 ... 2^24");
@@ -2033,16 +2049,18 @@ static int set_source(acme_batch *b, int row, int kind, long long den, const lon
     R.den = kind == SRC_CONST ? 1 : den;
     R.tones = kind == SRC_MULTISINE || kind == SRC_NOISE ? tones : 0;
     const size_t NT = kind == SRC_MULTISINE ? N * (size_t)tones : N;
-    const bool sine = kind == SRC_SINE || kind == SRC_MULTISINE;
+    const bool sine = kind == SRC_SINE || kind == SRC_MULTISINE || kind == SRC_BURST;
     int rc = src_upload(offset, sizeof(double) * N, (const void **)&R.off);
     if (rc == ACME_OK && kind != SRC_CONST) rc = src_upload(amp, sizeof(double) * NT, (const void **)&R.amp);
     if (rc == ACME_OK && (sine || kind == SRC_NOISE)) rc = src_upload(f_num, sizeof(long long) * NT, (const void **)&R.fnum);
     if (rc == ACME_OK && sine) rc = src_upload(phase, sizeof(long long) * NT, (const void **)&R.phase);
     if (rc == ACME_OK && kind == SRC_TABLE) rc = src_upload(w, sizeof(double) * (size_t)den, (const void **)&R.w);
+    if (rc == ACME_OK && shape) rc = src_upload(shape, sizeof(long long) * 5 * N, (const void **)&R.shape);
     for (auto &e : b->os.ev) if (rc == ACME_OK && !e && be::event_create(&e) != 0) rc = fail(ACME_ERR_HIP, "hipEventCreate");      // (the host pipeline of run_os)
     if (rc != ACME_OK) {
         (void)be::dfree(const_cast<double *>(R.amp)); (void)be::dfree(const_cast<double *>(R.off)); (void)be::dfree(const_cast<double *>(R.w));
         (void)be::dfree(const_cast<long long *>(R.fnum)); (void)be::dfree(const_cast<long long *>(R.phase));
+        (void)be::dfree(const_cast<long long *>(R.shape));
         return rc;
     }
     acme_batch::Sources &S = b->src;
@@ -2074,6 +2092,14 @@ int acme_batch_set_source_multisine(acme_batch *b, int row, long long f_den, int
 int acme_batch_set_source_noise(acme_batch *b, int row, int dist, long long hold, long long *stream, const double *amp,
                                 const double *offset) {
     return set_source(b, row, SRC_NOISE, hold, stream, nullptr, nullptr, amp, offset, dist);
+}
+
+int acme_batch_set_source_pulse(acme_batch *b, int row, long long *shape, const double *amp, const double *offset) {
+    return set_source(b, row, SRC_PULSE, 1, nullptr, nullptr, nullptr, amp, offset, 1, shape);
+}
+int acme_batch_set_source_burst(acme_batch *b, int row, long long *shape, long long f_den, long long *f_num, long long *phase,
+                                const double *amp, const double *offset) {
+    return set_source(b, row, SRC_BURST, f_den, f_num, phase, nullptr, amp, offset, 1, shape);
 }
 
 int acme_batch_clear_source(acme_batch *b, int row) {

@@ -15,6 +15,21 @@
 //           UNIFORM   fma(amp_i, U, offset_i),  U = (2 x + 1 - 2^53) 2^-53 (exact, odd: in (-1, 1), never 0)
 //           GAUSSIAN  fma(amp_i, g, offset_i),  g = sqrt(-2 log(u1)) sin(th),  u1 = (x + 1) 2^-53,  th = phase_angle(r2, 2^32)
 //           a sample depends on (stream_i, row, q) alone: never on the slice, tile, thread or call that computes it
+//   PULSE   fma(amp_i, e, offset_i) with e the instance's trapezoid envelope: five integers per instance -- period P_i
+//           (1 ... 2^31 - 1), delay_i (0 ... P_i - 1), rise_i, on_i, fall_i >= 0 with rise + on + fall <= P_i -- and
+//           j = (n - delay_i) mod P_i, reduced exactly in 64-bit integers (n mod P_i first):
+//             e = (double)j / (double)rise                         j < rise
+//                 1.0                                              rise <= j < rise + on
+//                 (double)(rise + on + fall - j) / (double)fall    rise + on <= j < rise + on + fall
+//                 0.0                                              otherwise
+//           every integer is below 2^31, so the conversions are exact and a ramp sample is ONE correctly rounded division;
+//           with the final fma two roundings at most.  rise = fall = 0: high for exactly `on` samples per period (duty on / P)
+//   BURST   g = amp_i e (one rounded product, always formed), then fma(g, sin(th), offset_i) with th SINE's angle from
+//           (f_num_i n + phase_i) mod f_den: the SINE row bit for bit where e = 1, offset_i where e = 0.  The tone runs with the
+//           CLOCK, it does not restart per burst: a burst starts at a zero crossing of the tone when delay and P are multiples
+//           of the tone's period.  (The sine is evaluated where e = 0 too: the value is the same.)
+//           On an oversampled batch an ideal edge (rise = 0 or fall = 0) wants its row HELD (held_rows): the interpolator
+//           would ring on it
 //
 // One launch per time slice (acme_api.inc run_os, where the expand kernel sits for constant rows) writes the slice's full
 // [N][len][nu] block: sourced rows generated, the others gathered from the caller's rows.
@@ -35,6 +50,12 @@
 // rows the fourth (src_thread<SRC_MODE_NOISE_MULTI>, acme_source_noise_multi_kernel), every other launch the one it always
 // took.  A NOISE row keeps q and n mod hold of the thread's first sample (the row's and the thread's alone) and steps
 // them by dt div hold, dt mod hold with one conditional carry: no division per sample; only the key is the instance's.
+// A PULSE or BURST row keeps, per instance, j of the thread's first sample and the step dt mod P_i (the two reductions, where
+// SINE has its two), then j += step with one conditional subtraction per sample; j, the step, P and the thresholds rise,
+// rise + on, rise + on + fall are 32-bit values.  A launch with such a row and otherwise the first kernel's kinds takes the fifth
+// instantiation (src_thread<SRC_MODE_PULSE>, acme_source_pulse_kernel), one that also holds MULTISINE or NOISE rows the sixth,
+// which has every kind (src_thread<SRC_MODE_ALL>, acme_source_all_kernel); launches without such a row take exactly the four
+// kernels above.  In both, a SINE row is rendered as the BURST row of e = 1 (g = amp_i 1.0 = amp_i: the same bits).
 //
 // The per-thread functions are host + device code; the launchers below are __global__ launches under hipcc and plain
 // loops over (block, thread) otherwise (the CPU emulator of tests/emu compiles acme_api.inc, and with it this file, with
@@ -50,9 +71,11 @@
 namespace acme {
 
 constexpr int SRC_NONE = 0, SRC_CONST = 1, SRC_SINE = 2, SRC_TABLE = 3, SRC_MULTISINE = 4, SRC_NOISE = 5;      // (include/acme_hip.h: ACME_SOURCE_*)
+constexpr int SRC_PULSE = 6, SRC_BURST = 7;
 constexpr int SRC_UNIFORM = 0, SRC_GAUSSIAN = 1;    // a NOISE row's distribution (ACME_NOISE_*)
-// the source kernel's instantiations (src_plan): bit 0: the launch may hold MULTISINE rows; bit 1: NOISE rows
-constexpr int SRC_MODE_PLAIN = 0, SRC_MODE_MULTI = 1, SRC_MODE_NOISE = 2, SRC_MODE_NOISE_MULTI = 3;
+// the source kernel's instantiations (src_plan): bit 0: the launch may hold MULTISINE rows; bit 1: NOISE rows; bit 2: PULSE
+// or BURST rows (alone, or with both other bits: the instantiation of every kind)
+constexpr int SRC_MODE_PLAIN = 0, SRC_MODE_MULTI = 1, SRC_MODE_NOISE = 2, SRC_MODE_NOISE_MULTI = 3, SRC_MODE_PULSE = 4, SRC_MODE_ALL = 7;
 constexpr double SRC_2M53 = 1.0 / 9007199254740992.0;      // 2^-53: the scale of a NOISE row's 53-bit draw
 constexpr int SRC_MAX_TONES = 4;            // tones of a MULTISINE row (ACME_MAX_SOURCE_TONES)
 constexpr long long SRC_MAX_TABLE = 1ll << 24;
@@ -62,7 +85,7 @@ constexpr int SRC_INST = 4;                 // instances per block
 constexpr int SRC_LDS = 4096;               // doubles of LDS for the table rows' windows (32 KB)
 
 // one input row (an array of 64 in device memory; the per-instance arrays [n], NULL = the default for every instance)
-struct SrcRow {
+struct alignas(128) SrcRow {        // (a power of two apart: a row is addressed by a shift, as it was at 64 bytes)
     int kind;                   // SRC_*; SRC_NONE: the caller's row
     int var;                    // SRC_NONE: the row's place among the caller's rows
     long long den;              // SINE, MULTISINE: f_den; TABLE: P; NOISE: hold
@@ -70,6 +93,7 @@ struct SrcRow {
     const long long *fnum, *phase;      // default 0, 0; NOISE: fnum holds the streams (default: stream_i = i)
     const double *w;            // TABLE: [P]
     int tones;                  // MULTISINE: amp, fnum, phase are [tones][n] (tone k of instance i at [k * n + i]); NOISE: SRC_UNIFORM / _GAUSSIAN
+    const long long *shape;     // PULSE, BURST: [5][n] -- period, delay, rise, on, fall (entry k of instance i at [k * n + i])
 };
 
 struct SrcArgs {
@@ -147,13 +171,27 @@ template <class Base> struct SrcRunNoise : Base {
     unsigned long long q;
     unsigned int key0, key1;
 };
+// a PULSE or BURST row beside those: the integer block, and what the per-instance reductions need of the thread ...
+template <class Base> struct SrcSlotPulse : Base {
+    const long long *shape;
+    unsigned long long first;   // the thread's first sample within the slice
+    unsigned int dt;            // samples per step
+};
+// ... and the instance's envelope: the running j, its step, the period and the thresholds rise, rise + on, rise + on + fall
+template <class Base> struct SrcRunPulse : Base {
+    unsigned int j, jstep, per, t1, t2, t3;
+};
 template <int MODE> struct SrcRunOf { typedef SrcRun type; };
 template <> struct SrcRunOf<SRC_MODE_MULTI> { typedef SrcRunMulti type; };
 template <> struct SrcRunOf<SRC_MODE_NOISE> { typedef SrcRunNoise<SrcRun> type; };
 template <> struct SrcRunOf<SRC_MODE_NOISE_MULTI> { typedef SrcRunNoise<SrcRunMulti> type; };
+template <> struct SrcRunOf<SRC_MODE_PULSE> { typedef SrcRunPulse<SrcRun> type; };
+template <> struct SrcRunOf<SRC_MODE_ALL> { typedef SrcRunPulse<SrcRunNoise<SrcRunMulti> > type; };
 template <int MODE> struct SrcSlotOf { typedef SrcSlot type; };
 template <> struct SrcSlotOf<SRC_MODE_NOISE> { typedef SrcSlotNoise type; };
 template <> struct SrcSlotOf<SRC_MODE_NOISE_MULTI> { typedef SrcSlotNoise type; };
+template <> struct SrcSlotOf<SRC_MODE_PULSE> { typedef SrcSlotPulse<SrcSlot> type; };
+template <> struct SrcSlotOf<SRC_MODE_ALL> { typedef SrcSlotPulse<SrcSlotNoise> type; };
 
 // Philox4x32-10 (Salmon et al., SC'11; the Random123 constants): counter c, key k -> four words
 struct SrcWords { unsigned int r0, r1, r2, r3; };
@@ -187,7 +225,7 @@ ACME_HD inline void src_slot_init(const SrcArgs &A, int row, long long tb, long 
     S.kind = R.kind; S.var = R.var; S.tones = R.tones;
     S.amp = R.amp; S.off = R.off; S.fnum = R.fnum; S.phase = R.phase; S.tab = R.w;
     S.den = 1; S.m0 = 0; S.dstep = 0;
-    if (R.kind == SRC_SINE || ((MODE & SRC_MODE_MULTI) && R.kind == SRC_MULTISINE)) {
+    if (R.kind == SRC_SINE || ((MODE & SRC_MODE_MULTI) && R.kind == SRC_MULTISINE) || ((MODE & SRC_MODE_PULSE) && R.kind == SRC_BURST)) {
         S.den = (unsigned long long)R.den;
         S.m0 = ((unsigned long long)(A.n0 % R.den) + (unsigned long long)(tb + ts)) % S.den;      // (n mod f_den first)
         S.dstep = (unsigned long long)dt % S.den;
@@ -215,6 +253,16 @@ ACME_HD inline void src_slot_init(const SrcArgs &A, int row, long long tb, long 
     S.den = hold;
     S.q0 = n / hold; S.m0 = n % hold;
     S.dq = (unsigned long long)dt / hold; S.dstep = (unsigned long long)dt % hold;
+}
+
+// ... of a launch that may hold PULSE or BURST rows
+template <int MODE, class Base>
+ACME_HD inline void src_slot_init(const SrcArgs &A, int row, long long tb, long long tl, long long ts, long long dt, const double *lds,
+                                  SrcSlotPulse<Base> &S) {
+    src_slot_init<MODE>(A, row, tb, tl, ts, dt, lds, static_cast<Base &>(S));
+    S.shape = A.rows[row].shape;
+    S.first = (unsigned long long)(tb + ts);
+    S.dt = (unsigned int)dt;
 }
 
 ACME_HD inline void src_run_init(const SrcArgs &A, const SrcSlot &S, long long i, long long tb, long long ts, SrcRun &R) {
@@ -262,6 +310,37 @@ ACME_HD inline void src_run_init(const SrcArgs &A, const SrcSlotNoise &S, long l
     R.key0 = (unsigned int)stream; R.key1 = (unsigned int)(stream >> 32);
 }
 
+// ... of a launch that may hold PULSE or BURST rows: j = (n - delay_i) mod P_i of the thread's first sample (n mod P_i first)
+// and the step dt mod P_i; the thresholds; a BURST row's tone as a SINE row's
+template <class SlotBase, class RunBase>
+ACME_HD inline void src_run_init(const SrcArgs &A, const SrcSlotPulse<SlotBase> &S, long long i, long long tb, long long ts,
+                                 SrcRunPulse<RunBase> &R) {
+    src_run_init(A, static_cast<const SlotBase &>(S), i, tb, ts, static_cast<RunBase &>(R));
+    R.j = 0u; R.jstep = 0u; R.per = 1u; R.t1 = 0u; R.t2 = 0u; R.t3 = 0u;
+    if (S.kind != SRC_PULSE && S.kind != SRC_BURST) return;
+    const unsigned long long P = (unsigned long long)S.shape[i], delay = (unsigned long long)S.shape[A.n + i];
+    const unsigned long long m = ((unsigned long long)(A.n0 % (long long)P) + S.first) % P;         // n mod P_i
+    R.per = (unsigned int)P;
+    R.j = (unsigned int)(m >= delay ? m - delay : m + P - delay);
+    R.jstep = S.dt % R.per;
+    R.t1 = (unsigned int)S.shape[2 * A.n + i];
+    R.t2 = R.t1 + (unsigned int)S.shape[3 * A.n + i];
+    R.t3 = R.t2 + (unsigned int)S.shape[4 * A.n + i];
+    if (S.kind == SRC_BURST) {
+        const unsigned long long f = S.fnum ? (unsigned long long)S.fnum[i] : 0ull, p = S.phase ? (unsigned long long)S.phase[i] : 0ull;
+        R.k = (f * S.m0 + p) % S.den;
+        R.step = (f * S.dstep) % S.den;
+    }
+}
+
+// the trapezoid at j: one division on the ramps (exact conversions: the integers are below 2^31), no a * b + c shape anywhere
+ACME_HD inline double src_envelope(unsigned int j, unsigned int t1, unsigned int t2, unsigned int t3) {
+    if (j < t1) return (double)j / (double)t1;
+    if (j < t2) return 1.0;
+    if (j < t3) return (double)(t3 - j) / (double)(t3 - t2);
+    return 0.0;
+}
+
 // the row's value at the thread's current sample; on to the next (dt samples later)
 ACME_HD inline double src_next(const SrcSlot &S, SrcRun &R, long long ustep) {
     double v;
@@ -305,6 +384,25 @@ ACME_HD inline double src_next(const SrcSlotNoise &S, SrcRunNoise<Base> &R, long
     R.k += R.step;
     R.q += S.dq;
     if (R.k >= S.den) { R.k -= S.den; ++R.q; }
+    return v;
+}
+
+// ... of a launch that may hold PULSE or BURST rows; a SINE row goes the BURST row's way with e = 1 (one sine in the code)
+template <class SlotBase, class RunBase>
+ACME_HD inline double src_next(const SrcSlotPulse<SlotBase> &S, SrcRunPulse<RunBase> &R, long long ustep) {
+    if (S.kind != SRC_PULSE && S.kind != SRC_BURST && S.kind != SRC_SINE)
+        return src_next(static_cast<const SlotBase &>(S), static_cast<RunBase &>(R), ustep);
+    double e = 1.0;
+    if (S.kind != SRC_SINE) {
+        e = src_envelope(R.j, R.t1, R.t2, R.t3);
+        R.j += R.jstep;                 // (both below P_i < 2^31)
+        if (R.j >= R.per) R.j -= R.per;
+        if (S.kind == SRC_PULSE) return fma(R.amp, e, R.off);
+    }
+    const double g = R.amp * e;
+    const double v = fma(g, sin(phase_angle((long long)R.k, (long long)S.den)), R.off);
+    R.k += R.step;
+    if (R.k >= S.den) R.k -= S.den;
     return v;
 }
 
@@ -356,7 +454,9 @@ inline void src_plan(SrcArgs &A, const SrcRow *host_rows, bool use_lds) {
     A.lds_rows = 0ull;
     A.mode = SRC_MODE_PLAIN;
     for (int r = 0; r < A.nu; ++r)
-        A.mode |= host_rows[r].kind == SRC_MULTISINE ? SRC_MODE_MULTI : host_rows[r].kind == SRC_NOISE ? SRC_MODE_NOISE : 0;
+        A.mode |= host_rows[r].kind == SRC_MULTISINE ? SRC_MODE_MULTI : host_rows[r].kind == SRC_NOISE ? SRC_MODE_NOISE
+                  : host_rows[r].kind == SRC_PULSE || host_rows[r].kind == SRC_BURST ? SRC_MODE_PULSE : 0;
+    if (A.mode > SRC_MODE_PULSE) A.mode = SRC_MODE_ALL;         // (PULSE / BURST next to MULTISINE or NOISE rows: the kernel of every kind)
     for (int r = 0; r < A.nu && use_lds; ++r) {
         if (host_rows[r].kind != SRC_TABLE) continue;
         const long long win = host_rows[r].den < tmax ? host_rows[r].den : tmax;
@@ -413,6 +513,24 @@ __global__ __launch_bounds__(acme::SRC_BLOCK, 2) void acme_source_noise_multi_ke
     }
     acme::src_thread<acme::SRC_MODE_NOISE_MULTI>(A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
 }
+__global__ __launch_bounds__(acme::SRC_BLOCK) void acme_source_pulse_kernel(acme::SrcArgs A) {
+    __shared__ double lds[acme::SRC_LDS];
+    if (A.lds_rows) {           // (uniform over the launch; PULSE and BURST rows use no LDS)
+        acme::src_stage(A, blockIdx.y, threadIdx.x, lds);
+        __syncthreads();
+    }
+    acme::src_thread<acme::SRC_MODE_PULSE>(A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
+// (every kind in one launch: two waves per SIMD as acme_source_noise_multi_kernel, and for its reason; correct for every
+// combination of kinds, not measured for speed -- DESIGN 2.5q)
+__global__ __launch_bounds__(acme::SRC_BLOCK, 2) void acme_source_all_kernel(acme::SrcArgs A) {
+    __shared__ double lds[acme::SRC_LDS];
+    if (A.lds_rows) {           // (uniform over the launch)
+        acme::src_stage(A, blockIdx.y, threadIdx.x, lds);
+        __syncthreads();
+    }
+    acme::src_thread<acme::SRC_MODE_ALL>(A, blockIdx.x, blockIdx.y, threadIdx.x, lds);
+}
 __global__ __launch_bounds__(256) void acme_source_copy_kernel(acme::SrcCopyArgs A) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx < A.n * A.len * A.rows) acme::src_copy(A, idx);
@@ -420,7 +538,9 @@ __global__ __launch_bounds__(256) void acme_source_copy_kernel(acme::SrcCopyArgs
 namespace acme {
 inline int src_launch(const SrcArgs &A, hipStream_t st) {
     const dim3 grid((unsigned)((A.n + SRC_INST - 1) / SRC_INST), (unsigned)((A.len + SRC_TILE - 1) / SRC_TILE));
-    if (A.mode == SRC_MODE_NOISE_MULTI) hipLaunchKernelGGL(acme_source_noise_multi_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
+    if (A.mode == SRC_MODE_ALL) hipLaunchKernelGGL(acme_source_all_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
+    else if (A.mode == SRC_MODE_PULSE) hipLaunchKernelGGL(acme_source_pulse_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
+    else if (A.mode == SRC_MODE_NOISE_MULTI) hipLaunchKernelGGL(acme_source_noise_multi_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
     else if (A.mode == SRC_MODE_NOISE) hipLaunchKernelGGL(acme_source_noise_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
     else if (A.mode == SRC_MODE_MULTI) hipLaunchKernelGGL(acme_source_multi_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
     else hipLaunchKernelGGL(acme_source_kernel, grid, dim3(SRC_BLOCK), 0, st, A);
@@ -439,7 +559,9 @@ inline int src_launch(const SrcArgs &A, void *) {
         for (int tid = 0; tid < SRC_BLOCK && A.lds_rows; ++tid) src_stage(A, by, tid, lds.data());
         for (long long bx = 0; bx * SRC_INST < A.n; ++bx)
             for (int tid = 0; tid < SRC_BLOCK; ++tid) {
-                if (A.mode == SRC_MODE_NOISE_MULTI) src_thread<SRC_MODE_NOISE_MULTI>(A, bx, by, tid, lds.data());
+                if (A.mode == SRC_MODE_ALL) src_thread<SRC_MODE_ALL>(A, bx, by, tid, lds.data());
+                else if (A.mode == SRC_MODE_PULSE) src_thread<SRC_MODE_PULSE>(A, bx, by, tid, lds.data());
+                else if (A.mode == SRC_MODE_NOISE_MULTI) src_thread<SRC_MODE_NOISE_MULTI>(A, bx, by, tid, lds.data());
                 else if (A.mode == SRC_MODE_NOISE) src_thread<SRC_MODE_NOISE>(A, bx, by, tid, lds.data());
                 else if (A.mode == SRC_MODE_MULTI) src_thread<SRC_MODE_MULTI>(A, bx, by, tid, lds.data());
                 else src_thread<SRC_MODE_PLAIN>(A, bx, by, tid, lds.data());

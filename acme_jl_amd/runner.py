@@ -64,7 +64,8 @@ ABI_SYMBOLS = [
     "acme_batch_set_source_const", "acme_batch_set_source_sine", "acme_batch_set_source_table", "acme_batch_clear_source",
     "acme_batch_set_source_clock", "acme_batch_get_source_clock", "acme_batch_run_sources", "acme_batch_run_sources_async",
     "acme_batch_render_sources",
-    "acme_batch_set_source_multisine", "acme_batch_set_source_noise", "acme_batch_set_measurement_bins",
+    "acme_batch_set_source_multisine", "acme_batch_set_source_noise", "acme_batch_set_source_pulse", "acme_batch_set_source_burst",
+    "acme_batch_set_measurement_bins",
     "acme_batch_set_measurement_series", "acme_batch_get_measurement_series",
     "acme_batch_set_measurement_fold", "acme_batch_get_measurement_fold", "acme_batch_get_measurement_fold_sums",
     "acme_batch_set_measurement_spectrum", "acme_batch_get_measurement_spectrum", "acme_batch_get_measurement_spectrum_sums",
@@ -78,7 +79,8 @@ ABI_SYMBOLS = [
     "acme_batch_set_measurement_events", "acme_batch_get_measurement_events",
 ]
 
-SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE, SOURCE_NOISE = 1, 2, 3, 4, 5
+SOURCE_CONST, SOURCE_SINE, SOURCE_TABLE, SOURCE_MULTISINE, SOURCE_NOISE, SOURCE_PULSE, SOURCE_BURST = 1, 2, 3, 4, 5, 6, 7
+MAX_PULSE_PERIOD = 2 ** 31 - 1
 NOISE_UNIFORM, NOISE_GAUSSIAN = 0, 1
 MAX_SOURCE_TONES = 4
 MAX_FOLD_PERIOD = 65536
@@ -93,7 +95,8 @@ MAX_EVENTS = 16777216
 EVENT_RISE, EVENT_FALL, EVENT_HIGH, EVENT_LOW, EVENT_UNKNOWN = 0, 1, 2, 3, 4
 _SOURCE_KINDS = {"const": SOURCE_CONST, "sine": SOURCE_SINE, "table": SOURCE_TABLE, "multisine": SOURCE_MULTISINE, "noise": SOURCE_NOISE,
                  SOURCE_CONST: SOURCE_CONST, SOURCE_SINE: SOURCE_SINE, SOURCE_TABLE: SOURCE_TABLE, SOURCE_MULTISINE: SOURCE_MULTISINE,
-                 SOURCE_NOISE: SOURCE_NOISE}
+                 SOURCE_NOISE: SOURCE_NOISE, "pulse": SOURCE_PULSE, "burst": SOURCE_BURST, "step": SOURCE_PULSE,
+                 SOURCE_PULSE: SOURCE_PULSE, SOURCE_BURST: SOURCE_BURST}
 _NOISE_DISTS = {"uniform": NOISE_UNIFORM, "gaussian": NOISE_GAUSSIAN, NOISE_UNIFORM: NOISE_UNIFORM, NOISE_GAUSSIAN: NOISE_GAUSSIAN}
 
 
@@ -208,6 +211,8 @@ class Library:
         L.acme_batch_render_sources.argtypes = [vp, vp, vp, C.c_longlong, C.c_int, vp]
         L.acme_batch_set_source_multisine.argtypes = [vp, C.c_int, C.c_longlong, C.c_int, lp, lp, dp, dp]
         L.acme_batch_set_source_noise.argtypes = [vp, C.c_int, C.c_int, C.c_longlong, lp, dp, dp]
+        L.acme_batch_set_source_pulse.argtypes = [vp, C.c_int, lp, dp, dp]
+        L.acme_batch_set_source_burst.argtypes = [vp, C.c_int, lp, C.c_longlong, lp, lp, dp, dp]
         L.acme_batch_set_measurement_bins.argtypes = [vp, C.c_longlong, C.c_longlong, C.c_longlong, C.c_int, lp, C.c_int, ip,
                                                       C.c_ulonglong]
         L.acme_batch_set_measurement_series.argtypes = [vp, C.c_longlong, C.c_longlong, C.c_longlong]
@@ -1134,13 +1139,13 @@ class ModelRunner:
 
         A fundamental PER INSTANCE (``acme_batch_set_measurement_per_instance``) instead of ``f0``: ``f_den`` with ``f_num``,
         a scalar or N integers -- instance i correlates with f_num[i] / f_den of the sample rate --, or
-        ``f0_from_source=row``: the ``f_den`` / ``f_num`` of the sine source armed on input row ``row`` (``set_source``).  A
+        ``f0_from_source=row``: the ``f_den`` / ``f_num`` of the sine source (or the burst source's tone) armed on input row ``row`` (``set_source``).  A
         window of ``length=f_den`` samples holds whole periods of every instance's fundamental."""
         if f0_from_source is not None:
             if f0 is not None or f_num is not None or f_den is not None:
                 raise ValueError("f0_from_source excludes f0 and f_den / f_num")
             src = self._sources.get(int(f0_from_source))
-            if src != SOURCE_SINE:
+            if src not in (SOURCE_SINE, SOURCE_BURST):       # (a burst's tone is a sine's)
                 raise ValueError(f"input row {f0_from_source} has no sine source to take the fundamental from")
             f_den, f_num = self._sine[int(f0_from_source)]
         if f_num is None and f_den is None:
@@ -1649,8 +1654,24 @@ class ModelRunner:
             raise DimensionMismatch(f"{what} must be integers")
         return arr, arr.ctypes.data_as(C.POINTER(C.c_double if dtype is np.float64 else C.c_longlong)), src.shape[0]
 
+    def _pulse_shape(self, kind, period, delay, rise, on, fall, at):
+        """the (5, N) integer block of a pulse or burst row -- period, delay, rise, on, fall, each a scalar or N values --;
+        ``kind="step"``: P = 2^31 - 1, delay = at, on = P - at - rise"""
+        if kind == "step":
+            if period is not None or on is not None or delay is not None or fall is not None:
+                raise ValueError("a step source takes at= and rise= (period, delay, on and fall are its own)")
+            at_, rise_ = self._per_instance(0 if at is None else at, np.int64, "at")[0], self._per_instance(0 if rise is None else rise, np.int64, "rise")[0]
+            period, delay, rise, on, fall = MAX_PULSE_PERIOD, at_, rise_, MAX_PULSE_PERIOD - at_ - rise_, 0
+        elif at is not None:
+            raise ValueError("at= belongs to a step source")
+        elif period is None or on is None:
+            raise ValueError("a pulse or burst source needs period and on")
+        cols = [self._per_instance(0 if v is None else v, np.int64, what)[0]
+                for v, what in ((period, "period"), (delay, "delay"), (rise, "rise"), (on, "on"), (fall, "fall"))]
+        return np.ascontiguousarray(np.stack(cols))
+
     def set_source(self, row, kind, amp=None, offset=None, f_den=None, f_num=None, phase=None, table=None,
-                   dist="gaussian", hold=1, stream=None, seed=0):
+                   dist="gaussian", hold=1, stream=None, seed=0, period=None, delay=None, rise=None, on=None, fall=None, at=None):
         """Give input row ``row`` a source (``acme_batch_set_source_*``): the library generates the row on the device, at
         source clock n (base-rate samples since the first source was armed) for instance i
 
@@ -1668,14 +1689,47 @@ class ModelRunner:
           ``hold`` samples aligned to the clock (1: white noise; larger: stepped random values, a jumping pot).  ``stream``:
           N integers (equal streams on a row render equal sequences; the same stream on two rows independent ones);
           otherwise ``stream[i] = seed * 2^32 + i`` with ``0 <= seed < 2^31``
+        * ``"pulse"``: ``fma(amp[i], e, offset[i])`` with e a per-instance trapezoid: ``period`` (1 ... 2^31 - 1), ``delay``
+          (0 ... period - 1, default 0), ``rise``, ``on``, ``fall`` (>= 0, rise + on + fall <= period; rise and fall default 0),
+          each a scalar or N integers; with j = (n - delay[i]) mod period[i], e = j / rise on the rising ramp, 1 for ``on``
+          samples, (rise + on + fall - j) / fall on the falling ramp, 0 otherwise -- one division per ramp sample, so the row
+          is pinned bit for bit.  rise = fall = 0: high for exactly ``on`` samples per period (duty on / period).  A PWM or
+          duty sweep, an edge-time sweep, a delay scan are each one batch
+        * ``"step"``: ``set_source(row, "step", at=d, rise=0, amp=, offset=)`` -- the pulse with period P = 2^31 - 1,
+          delay = d, on = P - d - rise: ``offset`` before clock d, a ramp of ``rise`` samples, then ``offset + amp``; a long
+          ``rise`` is a ramp-and-hold of a pot row.  It WRAPS at clock 2^31 - 1 + d (13.5 hours at 44.1 kHz)
+        * ``"burst"``: a tone burst, ``g = amp[i] e`` then ``fma(g, sin(th), offset[i])`` with e the pulse's envelope (the same
+          five keywords) and th the ``"sine"`` row's angle from ``f_den``, ``f_num``, ``phase`` (the TONE's phase): the sine row
+          bit for bit where e = 1, ``offset`` where e = 0.  The tone runs with the clock, it does not restart per burst: a
+          burst starts at a zero crossing when ``delay`` and ``period`` are multiples of the tone's period.  The row lends
+          its frequency to ``set_measurement(f0_from_source=)`` as a sine row does
 
+        On an oversampled batch an ideal edge (rise = 0 or fall = 0) wants its row in ``held_rows``.
         ``amp``, ``offset``, ``f_num``, ``phase``: None (amp 1, the others 0), a scalar or N values.  ``run_sources`` then runs
         without these rows; its results are those of ``run`` on ``render_sources``' array, bit for bit."""
         k = _SOURCE_KINDS.get(kind)
         if k is None:
-            raise ValueError(f"unknown source kind {kind!r}: 'const', 'sine', 'multisine', 'table' or 'noise'")
+            raise ValueError(f"unknown source kind {kind!r}: 'const', 'sine', 'multisine', 'table', 'noise', 'pulse', 'step' or 'burst'")
         oa, op = self._per_instance(offset, np.float64, "offset")
         L = self.lib.L
+        if k in (SOURCE_PULSE, SOURCE_BURST):
+            shape = self._pulse_shape("step" if kind == "step" else "pulse", period, delay, rise, on, fall, at)
+            sp = shape.ctypes.data_as(C.POINTER(C.c_longlong))
+            aa, ap = self._per_instance(amp, np.float64, "amp")
+            if k == SOURCE_PULSE:
+                self.lib.check(L.acme_batch_set_source_pulse(self.h, int(row), sp, ap, op))
+                self._sine.pop(int(row), None)
+            else:
+                if f_den is None:
+                    raise ValueError("a burst source needs f_den")
+                fa, fp = self._per_instance(f_num, np.int64, "f_num")
+                pa, pp = self._per_instance(phase, np.int64, "phase")
+                self.lib.check(L.acme_batch_set_source_burst(self.h, int(row), sp, int(f_den), fp, pp, ap, op))
+                self._sine[int(row)] = (int(f_den), 0 if fa is None else fa.copy())
+            self._sources[int(row)] = k
+            return self
+        if any(v is not None for v in (period, delay, rise, on, fall, at)):
+            raise ValueError("period, delay, rise, on, fall and at belong to a pulse, step or burst source")
         if k == SOURCE_NOISE:
             d = _NOISE_DISTS.get(dist)
             if d is None:
@@ -2344,9 +2398,10 @@ class MultiDeviceRunner:
 
     # ---- sources: the per-instance parameters sliced over the devices ---------------------------
     def set_source(self, row, kind, amp=None, offset=None, f_den=None, f_num=None, phase=None, table=None,
-                   dist="gaussian", hold=1, stream=None, seed=0):
+                   dist="gaussian", hold=1, stream=None, seed=0, period=None, delay=None, rise=None, on=None, fall=None, at=None):
         """``ModelRunner.set_source`` on every device's batch, each with its instances' parameters (a noise source's
-        streams are formed over the global instance index: a sharded batch renders what the single batch renders)"""
+        streams are formed over the global instance index: a sharded batch renders what the single batch renders; a pulse's
+        or burst's five integers are sliced as the other parameters are)"""
         multi = _SOURCE_KINDS.get(kind) == SOURCE_MULTISINE
         streams = noise_streams(self.n, stream, seed) if _SOURCE_KINDS.get(kind) == SOURCE_NOISE else None
 
@@ -2356,7 +2411,7 @@ class MultiDeviceRunner:
             if multi and a is not offset:
                 return a                    # ((tones,): one value per tone for every instance)
             return a if a is None or np.ndim(a) == 0 else np.asarray(a)[lo:hi]
-        for a in (amp, offset, f_num, phase):
+        for a in (amp, offset, f_num, phase, period, delay, rise, on, fall, at):
             if multi and a is not offset:
                 if a is not None and np.ndim(a) == 2 and np.shape(a)[1] not in (1, self.n):
                     raise DimensionMismatch(f"per-instance tone parameters need (tones, {self.n}) values")
@@ -2365,7 +2420,8 @@ class MultiDeviceRunner:
         for r, (lo, hi) in zip(self.runners, self.ranges):
             if r is not None:
                 r.set_source(row, kind, part(amp, lo, hi), part(offset, lo, hi), f_den, part(f_num, lo, hi), part(phase, lo, hi), table,
-                             dist, hold, None if streams is None else streams[lo:hi], seed)
+                             dist, hold, None if streams is None else streams[lo:hi], seed, part(period, lo, hi), part(delay, lo, hi),
+                             part(rise, lo, hi), part(on, lo, hi), part(fall, lo, hi), part(at, lo, hi))
         return self
 
     def clear_source(self, row=-1):

@@ -746,7 +746,26 @@ int acme_batch_get_measurement(acme_batch *b, double *out, long long *count);
  *                         to the CLOCK (1: white noise at the base rate; larger: stepped random values, a jumping pot).
  *                         stream: a HOST array of N entries or NULL (stream_i = i); equal streams on one row render equal
  *                         sequences, the same stream on two rows independent ones
- *   parameters    amp, offset, f_num, phase: HOST arrays of N entries, copied to the device by the call (parameters, not
+ *     ACME_SOURCE_PULSE   fma(amp_i, e, offset_i), e a per-instance TRAPEZOID envelope: five integers per instance -- period P_i
+ *                         (1 ... 2^31 - 1), delay_i (0 ... P_i - 1), rise_i, on_i, fall_i >= 0 with rise + on + fall <= P_i --
+ *                         and j = (n - delay_i) mod P_i, reduced exactly in 64-bit integers (n mod P_i first: valid for clocks
+ *                         up to 2^62):
+ *                           e = (double)j / (double)rise                         j < rise
+ *                               1.0                                              rise <= j < rise + on
+ *                               (double)(rise + on + fall - j) / (double)fall    rise + on <= j < rise + on + fall
+ *                               0.0                                              otherwise
+ *                         The conversions are exact, a ramp sample is ONE correctly rounded division: with the fma two roundings
+ *                         at most, the row is reproducible bit for bit.  rise = fall = 0: high for exactly `on` samples per
+ *                         period, the duty cycle on / P exactly.  rise > 0: the sampled continuous trapezoid, 0 at j = 0, 1 at
+ *                         j = rise when on > 0 (or on = 0 and fall > 0; with on = fall = 0 it never reaches 1).  A step is a
+ *                         pulse of P = 2^31 - 1; a ramp-and-hold of a pot row a long rise on that step; a PWM or duty sweep, an
+ *                         edge-time sweep, a delay scan are each one batch
+ *     ACME_SOURCE_BURST   a tone burst: g = amp_i e (one rounded product), then fma(g, sin(th), offset_i) with e PULSE's
+ *                         envelope and th exactly SINE's angle from (f_num_i n + phase_i) mod f_den.  Where e = 1 the row is the
+ *                         SINE row bit for bit, where e = 0 it is offset_i.  The tone runs with the CLOCK, it does not restart per
+ *                         burst: a burst starts at a zero crossing when delay and P are multiples of the tone's period
+ *                         shape: a HOST array [5][N] -- period, delay, rise, on, fall; entry k of instance i at shape[k * N + i]
+ *   parameters   amp, offset, f_num, phase: HOST arrays of N entries, copied to the device by the call (parameters, not
  *                 signals); NULL = the same default for every instance (amp 1, the others 0).  w: a host array of P entries.
  *                 (f_num and phase are only read.)
  * DEFINING PROPERTY: acme_batch_run_sources produces, bit for bit, what acme_batch_run produces on the materialised u --
@@ -754,7 +773,8 @@ int acme_batch_get_measurement(acme_batch *b, double *out, long long *count);
  * oversampling histories; in host and device memory, with y stored or y = NULL (measurement armed), in split calls (T1 then
  * T2 = one run of T1 + T2), asynchronously, with the balancing on or off.  On an oversampled batch a sourced row is generated
  * at the BASE rate and then treated as a caller's row is: interpolated, or held if its bit is in held_rows; a CONST row is
- * always held (as the constant rows of acme_batch_run_const are).
+ * always held (as the constant rows of acme_batch_run_const are).  An ideal edge of a PULSE or BURST row (rise = 0 or
+ * fall = 0) wants the row HELD: interpolated, the band-limiting filter rings on it.
  * Runs go slice by slice on the launch stream (the source kernel, csrc/acme_source.h, ahead of the slice's interpolation /
  * run kernel); host buffers take the staged slice pipeline, never the streamed path of acme_batch_set_host_retention.  While
  * a row has a source, acme_batch_run, _run_const and _run_async return ACME_ERR_INVALID (rows of a full u would be silently
@@ -766,6 +786,8 @@ int acme_batch_get_measurement(acme_batch *b, double *out, long long *count);
 #define ACME_SOURCE_TABLE 3
 #define ACME_SOURCE_MULTISINE 4
 #define ACME_SOURCE_NOISE 5
+#define ACME_SOURCE_PULSE 6
+#define ACME_SOURCE_BURST 7
 #define ACME_NOISE_UNIFORM 0
 #define ACME_NOISE_GAUSSIAN 1
 #define ACME_MAX_SOURCE_TABLE 16777216
@@ -786,7 +808,14 @@ int acme_batch_set_source_multisine(acme_batch *b, int row, long long f_den, int
  * ACME_NOISE_UNIFORM nor ACME_NOISE_GAUSSIAN and a hold outside 1 ... 2^31 - 1. */
 int acme_batch_set_source_noise(acme_batch *b, int row, int dist, long long hold, long long *stream, const double *amp,
                                 const double *offset);
-/* the row is the caller's again; row < 0: every row.  With the last source the clock goes (the next first source starts
+/* shape: [5][N] (period, delay, rise, on, fall), required, only read; amp, offset: [N] or NULL.  ACME_ERR_INVALID, naming the
+ * instance, also for a null shape, a period outside 1 ... 2^31 - 1, a delay outside 0 ... period - 1, a negative rise, on or
+ * fall and rise + on + fall > period; the burst adds the sine's checks of f_den, f_num and phase (the tone's).  A refused call
+ * leaves the row as it was. */
+int acme_batch_set_source_pulse(acme_batch *b, int row, long long *shape, const double *amp, const double *offset);
+int acme_batch_set_source_burst(acme_batch *b, int row, long long *shape, long long f_den, long long *f_num,
+                                long long *phase, const double *amp, const double *offset);
+/* the row is the caller's again; row < 0: every row. With the last source the clock goes (the next first source starts
  * it at 0). */
 int acme_batch_clear_source(acme_batch *b, int row);
 /* the source clock (n >= 0); ACME_ERR_INVALID while no row has a source */

@@ -37,7 +37,7 @@ import ACME: run!, solve, hasconverged, needediterations, set_resabstol!,
 export BatchRunner, MultiBatchRunner, GPUBatchSolver, element_table, retain_host_buffers!, release_host_buffers!, set_isolation!, set_balance!,
        MeasureSpec, Measurement, set_measurement!, clear_measurement!, reset_measurement!, measurement, measurement_plan, measure!,
        set_source!, clear_source!, source_clock, source_clock!, run_sources!, render_sources,
-       set_source_multisine!, set_source_noise!, set_measurement_bins!, set_measurement_series!, measurement_series,
+       set_source_multisine!, set_source_noise!, set_source_pulse!, set_source_burst!, set_measurement_bins!, set_measurement_series!, measurement_series,
        set_measurement_fold!, measurement_fold, set_measurement_spectrum!, measurement_spectrum,
        set_measurement_cross!, measurement_cross, set_measurement_target!, measurement_target,
        set_measurement_weighting!, measurement_weighting, set_measurement_ensemble!, measurement_ensemble,
@@ -68,6 +68,7 @@ const ACME_MAX_EVENTS = 16777216
 const ACME_EVENT_RISE, ACME_EVENT_FALL, ACME_EVENT_HIGH, ACME_EVENT_LOW, ACME_EVENT_UNKNOWN = Cint(0), Cint(1), Cint(2), Cint(3), Cint(4)
 const ACME_SOURCE_CONST, ACME_SOURCE_SINE, ACME_SOURCE_TABLE, ACME_SOURCE_MULTISINE = Cint(1), Cint(2), Cint(3), Cint(4)
 const ACME_SOURCE_NOISE = Cint(5)
+const ACME_SOURCE_PULSE, ACME_SOURCE_BURST = Cint(6), Cint(7)
 const ACME_NOISE_UNIFORM, ACME_NOISE_GAUSSIAN = Cint(0), Cint(1)
 const ACME_MAX_SOURCE_TABLE = 16777216
 const ACME_MAX_SOURCE_TONES = 4
@@ -1098,6 +1099,49 @@ function set_source_noise!(r::BatchRunner, row::Integer; dist::Symbol=:gaussian,
     GC.@preserve s a o check(ccall((:acme_batch_set_source_noise, lib), Cint,
                 (Ptr{Cvoid}, Cint, Cint, Clonglong, Ptr{Clonglong}, Ptr{Cdouble}, Ptr{Cdouble}),
                 r.h, row - 1, d, hold, ptr_or_null(s), ptr_or_null(a), ptr_or_null(o)))
+    push!(r.sources, Int(row))
+    return r
+end
+
+# the [5][N] integer block of a pulse or burst row: period, delay, rise, on, fall (each a number or N values)
+pulse_shape(r::BatchRunner, period, delay, rise, on, fall) =
+    vcat(perinstance(Clonglong, period, r.n), perinstance(Clonglong, delay, r.n), perinstance(Clonglong, rise, r.n),
+         perinstance(Clonglong, on, r.n), perinstance(Clonglong, fall, r.n))
+
+"""
+    set_source_pulse!(runner, row; period, on, delay=0, rise=0, fall=0, amp=nothing, offset=nothing)
+
+Give input row `row` (1-based) a pulse source (`acme_batch_set_source_pulse`): `fma(amp[i], e, offset[i])` with e a per-instance
+trapezoid over j = (n - delay[i]) mod period[i] -- j / rise on the rising ramp, 1 for `on` samples, (rise + on + fall - j) / fall
+on the falling ramp, 0 otherwise; one correctly rounded division per ramp sample, so the row is pinned bit for bit.  `period`
+(1 ... 2^31 - 1), `delay` (0 ... period - 1), `rise`, `on`, `fall` (>= 0, rise + on + fall <= period): a number or N integers.
+A step is a pulse of period 2^31 - 1; a PWM or duty sweep, an edge-time sweep, a delay scan are each one batch.  On an
+oversampled batch an ideal edge wants the row in `held_rows`.
+"""
+function set_source_pulse!(r::BatchRunner, row::Integer; period, on, delay=0, rise=0, fall=0, amp=nothing, offset=nothing)
+    s, a, o = pulse_shape(r, period, delay, rise, on, fall), perinstance(Cdouble, amp, r.n), perinstance(Cdouble, offset, r.n)
+    GC.@preserve s a o check(ccall((:acme_batch_set_source_pulse, lib), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Clonglong}, Ptr{Cdouble}, Ptr{Cdouble}),
+                r.h, row - 1, pointer(s), ptr_or_null(a), ptr_or_null(o)))
+    push!(r.sources, Int(row))
+    return r
+end
+
+"""
+    set_source_burst!(runner, row; period, on, f_den, f_num=nothing, phase=nothing, delay=0, rise=0, fall=0, amp=nothing, offset=nothing)
+
+Give input row `row` (1-based) a tone burst (`acme_batch_set_source_burst`): g = amp[i] e, then `fma(g, sin(th), offset[i])` with
+e the envelope of `set_source_pulse!` and th the `:sine` row's angle from `f_den`, `f_num`, `phase` (the tone's).  Where e = 1
+the row is the sine row bit for bit, where e = 0 it is `offset[i]`.  The tone runs with the clock, it does not restart per
+burst: a burst starts at a zero crossing when `delay` and `period` are multiples of the tone's period.
+"""
+function set_source_burst!(r::BatchRunner, row::Integer; period, on, f_den::Integer, f_num=nothing, phase=nothing, delay=0, rise=0, fall=0,
+                           amp=nothing, offset=nothing)
+    s, a, o = pulse_shape(r, period, delay, rise, on, fall), perinstance(Cdouble, amp, r.n), perinstance(Cdouble, offset, r.n)
+    f, p = perinstance(Clonglong, f_num, r.n), perinstance(Clonglong, phase, r.n)
+    GC.@preserve s f p a o check(ccall((:acme_batch_set_source_burst, lib), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Clonglong}, Clonglong, Ptr{Clonglong}, Ptr{Clonglong}, Ptr{Cdouble}, Ptr{Cdouble}),
+                r.h, row - 1, pointer(s), f_den, ptr_or_null(f), ptr_or_null(p), ptr_or_null(a), ptr_or_null(o)))
     push!(r.sources, Int(row))
     return r
 end

@@ -8,10 +8,13 @@ y = NULL.  Milliseconds per second of audio (median over the steps) for
   sine1   the source kernel alone: one slice (4 096 samples) of ONE row, a SINE with per-instance frequencies, rendered
           to device memory; milliseconds per slice from device events
   table1  the same for a TABLE row of 44 100 entries
+  pulse1  the same for a PULSE row: per-instance periods (100 ... 20 099 samples), edges (rise and fall a tenth of the period
+          each) and widths
+  burst1  the same for a BURST row: pulse1's envelopes on sine1's tones
 The source and expand kernels' own times per slice inside a run: `rocprofv3 --kernel-trace --stats -- python
 tools/source_probe.py --legs src` (acme_source_kernel) and `--legs yard` (acme_expand_kernel), in runs of their own.
 
-    python tools/source_probe.py [--instances N] [--steps S] [--warmup W] [--legs yard,src,host,sine1,table1] [--tree DIR]
+    python tools/source_probe.py [--instances N] [--steps S] [--warmup W] [--legs yard,src,host,sine1,table1,pulse1,burst1] [--tree DIR]
 """
 import argparse
 import json
@@ -48,7 +51,7 @@ def main():
     st = torch.cuda.current_stream().cuda_stream
 
     for leg in legs:
-        if leg in ("sine1", "table1"):
+        if leg in ("sine1", "table1", "pulse1", "burst1"):
             from fractions import Fraction
             from acme_jl_amd import examples
             from acme_jl_amd.circuit import voltageprobe, voltagesource
@@ -57,8 +60,15 @@ def main():
             r = ModelRunner(wire, N, device=0)
             if leg == "sine1":
                 r.set_source(0, "sine", f_den=fs, f_num=20 + idx % 20000, amp=np.linspace(0.01, 1.0, N))
-            else:
+            elif leg == "table1":
                 r.set_source(0, "table", table=np.sin(2 * np.pi * 1000.0 / fs * np.arange(fs)), amp=np.linspace(0.01, 1.0, N))
+            else:
+                period = 100 + idx % 20000
+                env = dict(period=period, delay=idx % 97, rise=period // 10, on=period // 2, fall=period // 10, amp=np.linspace(0.01, 1.0, N))
+                if leg == "pulse1":
+                    r.set_source(0, "pulse", **env)
+                else:
+                    r.set_source(0, "burst", f_den=fs, f_num=20 + idx % 20000, **env)
             TS = 4096
             ud = torch.empty((N, TS, 1), dtype=torch.float64, device="cuda")
             ms = []
